@@ -11,6 +11,10 @@ timed region).  The same batch forward-only is BASELINE configs[1] (`fwd_only`).
 The path shards over independent images: no data-path collective in the micro-step, one all-reduce of the fp32 gradient arena per
 optimizer step, weak scaling.  One JSON line on rank 0.  `--extra-batch B` (default 24) adds the same measurement at B images per step
 under `batch_<B>` (the throughput-optimal micro-batch on 288 GB of HBM; 0 = skip).
+
+A plain run sets up, warms up, times the --steps steps, writes the last step's outputs when --dump-outputs DIR is given, and prints the
+result line.  Everything else -- the forward-only pass, the per-kernel roofline, the launch count, the gradient-exchange cost, the other
+batch sizes and configurations, the neighbouring paths, the CPU baseline -- runs only with --full (`--extra-batch`, `--no-*` act there).
 """
 import argparse
 import json
@@ -118,9 +122,19 @@ def timed(step, steps, warmup, dist, dev, after_warmup=None):
     return dt, out
 
 
-def measure(model, cfg, args, B, dev, dist, rank, world, local, use_graph, trainer_cls):
-    """Train-mode (fwd+bwd, optimizer step every --accum micro-steps) and forward-only throughput at B images per rank per step, plus
-    the per-kernel GEMM timing (HIP events on the launch stream, eager launches of the same step function)."""
+def dump_outputs(out, d):
+    """What the timed step returned to its caller (the loss dict of `micro_step` / `model_forward`) as DIR/<name>.npy, float32."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            np.save(os.path.join(d, f"{k}.npy"), v.detach().float().cpu().numpy())
+
+
+def measure(model, cfg, args, B, dev, dist, rank, world, local, use_graph, trainer_cls, dump_dir=None):
+    """Train-mode (fwd+bwd, optimizer step every --accum micro-steps) throughput at B images per rank per step; with --full also the
+    forward-only throughput and the per-kernel GEMM timing (HIP events on the launch stream, eager launches of the same step function).
+    dump_dir: where the last timed step's outputs go (`dump_outputs`), written right after the timed region."""
     from llmseg_amd import ops, synthetic
     img = 1024 if args.backbone == "sam" else 896
     batch = synthetic.make_batch(B, img_size=img, L=args.prompt_len, K=args.masks, device=dev, seed=1234 + rank)
@@ -146,6 +160,10 @@ def measure(model, cfg, args, B, dev, dist, rank, world, local, use_graph, train
                    graph=bool(use_graph and trainer.graph_error is None and any(e["graph"] is not None for e in trainer._graphs.values())))
         if trainer.graph_error:
             res["graph_error"] = trainer.graph_error[:200]
+        if dump_dir:
+            dump_outputs(out, dump_dir)
+        if not args.full:
+            return res
         if dist is not None and trainer.arena is not None:
             # what the data-parallel exchange costs: `exposed_ms` = compute-stream time per optimizer step from issuing the collectives to holding the
             # reduced arena + its norm (inside the timed region: nothing overlaps it); `allreduce_ms` = the same buffers exchanged alone
@@ -206,6 +224,10 @@ def measure(model, cfg, args, B, dev, dist, rank, world, local, use_graph, train
                 return model.model_forward(**batch, inference=False, plan=plan)
         dt, out = timed(fstep, args.steps, args.warmup, dist, dev)
         res.update(value=B * world * args.steps / dt, ms_per_step=dt / args.steps * 1e3, loss=float(out["loss"]), graph=False)
+        if dump_dir:
+            dump_outputs(out, dump_dir)
+        if not args.full:
+            return res
         overlap, model.overlap_towers = model.overlap_towers, False
         ops.prof_enable(True)
         n_prof = min(args.steps, 3)
@@ -495,8 +517,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=2, help="images per rank per micro-step (BASELINE configs[2]: batch_size=2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement and check as well (forward-only, roofline, other batch sizes and "
+                         "configurations, neighbouring paths, CPU baseline); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (the loss dict the step returns) to DIR/<name>.npy as float32")
     ap.add_argument("--extra-batch", type=int, default=24,
-                    help="also measure this many images per micro-step (24: every Llama GEMM, M = 24 x 319 rows, fills whole rounds of "
+                    help="with --full: also measure this many images per micro-step (24: every Llama GEMM, M = 24 x 319 rows, fills whole rounds of "
                          "256 x 256 tiles) and report it under batch_<B>; 0 = skip")
     ap.add_argument("--backbone", default="sam", choices=["sam", "dinov2"])
     ap.add_argument("--masks", type=int, default=256)
@@ -600,12 +627,14 @@ def main():
         if dist:
             dist.barrier(); dist.destroy_process_group()
         return
-    main_res = measure(model, cfg, args, args.batch, dev, dist, rank, world, local, use_graph, Trainer)
+    main_res = measure(model, cfg, args, args.batch, dev, dist, rank, world, local, use_graph, Trainer,
+                       dump_dir=args.dump_outputs if rank == 0 else None)
+    full = args.full
     extra = None
-    if args.extra_batch and args.extra_batch != args.batch:
+    if full and args.extra_batch and args.extra_batch != args.batch:
         extra = measure(model, cfg, args, args.extra_batch, dev, dist, rank, world, local, use_graph, Trainer)
     k512 = None
-    if train and not args.no_k512 and not args.small:
+    if full and train and not args.no_k512 and not args.small:
         # BASELINE configs[4]'s workload shape on this model: 512 candidate masks per image, gradient accumulation 8 (training.py:79-82)
         a4 = argparse.Namespace(**vars(args))
         a4.masks, a4.accum, a4.no_fwd_only = 512, 8, True
@@ -613,20 +642,20 @@ def main():
         k512 = measure(model, cfg, a4, args.batch, dev, dist, rank, world, local, use_graph, Trainer)
         k512["workload"] = "BASELINE.json configs[4] shape: %d candidate masks per image, grad-accum %d, %d timed micro-steps" % (a4.masks, a4.accum, a4.steps)
     fused = None
-    if train and use_graph and not args.no_accum_fused and args.accum > 1:
+    if full and train and use_graph and not args.no_accum_fused and args.accum > 1:
         fused = accum_fused(model, cfg, args, args.batch, dev, dist, rank, world, local, Trainer)
     wtow = None
-    if train and use_graph and not args.no_window_towers and args.accum > 1:
+    if full and train and use_graph and not args.no_window_towers and args.accum > 1:
         wtow = window_towers(model, cfg, args, args.batch, dev, dist, rank, world, local, Trainer)
     mix = None
-    if train and use_graph and not args.no_mix and not args.small:
+    if full and train and use_graph and not args.no_mix and not args.small:
         mix = mix_9_3_1(model, cfg, args, dev, dist, rank, world, local, Trainer)
         if not args.no_window_towers:
             from llmseg_amd import synthetic
             sampler = synthetic.HybridSampler((9, 3, 1), seed=2024 + rank)
             mix["window_towers"] = window_towers(model, cfg, args, 1, dev, dist, rank, world, local, Trainer, convs=[sampler.draw()[1] for _ in range(args.accum)])
     loader = None
-    if train and use_graph and not args.no_loader and not args.small:
+    if full and train and use_graph and not args.no_loader and not args.small:
         loader = loader_in_loop(model, cfg, args, args.batch, dev, dist, rank, world, local, Trainer, main_res["ms_per_step"])
 
     if rank == 0:
@@ -646,16 +675,16 @@ def main():
                        "images_per_gpu_per_step": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world}",
                        "process_group_world_size": (dist.get_world_size() if dist else None),     # what RCCL reports (None: no process group at 1 GPU)
                        "graph": main_res.get("graph", False), "valid": not args.small},
+        }
+        if full:
             # dominant kernel = the GEMM kernel class with the largest total time; achieved = its algorithmic 2MNK per launch / its
             # HIP-event duration
-            "roofline": main_res["roofline"],
-            "model_tflop_per_image": main_res["model_tflop_per_image"],
-            "model_mfma_frac": main_res["model_mfma_frac"],
-            "loss": main_res["loss"],
-            "launches_per_micro_step": main_res.get("launches_per_micro_step"),
-            "grad_exchange": main_res.get("grad_exchange"),
-            "peak_hbm_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
-        }
+            res.update(roofline=main_res["roofline"], model_tflop_per_image=main_res["model_tflop_per_image"],
+                       model_mfma_frac=main_res["model_mfma_frac"])
+        res["loss"] = main_res["loss"]
+        if full:
+            res.update(launches_per_micro_step=main_res.get("launches_per_micro_step"), grad_exchange=main_res.get("grad_exchange"))
+        res["peak_hbm_gb"] = torch.cuda.max_memory_allocated() / 2 ** 30
         if "graph_error" in main_res:
             res["graph_error"] = main_res["graph_error"]
         if "fwd_only" in main_res:
@@ -672,9 +701,9 @@ def main():
             res["mix_9_3_1_batch_1"] = mix
         if loader is not None:
             res["loader_in_loop"] = loader
-        if world == 1 and not args.no_neighbours and not args.small and args.backbone == "sam":
+        if full and world == 1 and not args.no_neighbours and not args.small and args.backbone == "sam":
             res["neighbours"] = neighbours(model, cfg, dev, args.prompt_len)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
     else:
         res = None

@@ -60,9 +60,9 @@ def test_world1_process_group_paths():
 
 def test_bench_under_torchrun_world1():
     """bench.py through `torch.distributed.run` (1 rank) with the process group forced on: the launch line, env parsing, barrier /
-    all_reduce(MAX) timing, teardown and the JSON contract."""
+    all_reduce(MAX) timing, teardown and the JSON contract, with the side measurements of --full."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29573",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--small", "--extra-batch", "0", "--no-cpu-baseline", "--force-dist"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--small", "--extra-batch", "0", "--no-cpu-baseline", "--force-dist", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]

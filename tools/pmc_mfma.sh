@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_mfma_$TAG
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA GRBM_GUI_ACTIVE \
-  --kernel-include-regex "gemm_bf16|attn_" --output-format csv -d /tmp/pmc_mfma_$TAG -o p -- python $R/bench.py --no-cpu-baseline --no-neighbours --no-k512 --no-loader --no-fwd-only --no-overlap --no-graph "$@" > $OUT/pmc_mfma_$TAG.log 2>&1
+  --kernel-include-regex "gemm_bf16|attn_" --output-format csv -d /tmp/pmc_mfma_$TAG -o p -- python $R/bench.py --full --no-cpu-baseline --no-neighbours --no-k512 --no-loader --no-fwd-only --no-overlap --no-graph "$@" > $OUT/pmc_mfma_$TAG.log 2>&1
 echo "pmc rc=$?"
 python - "$TAG" "$OUT" "$*" <<'PY'
 import csv, glob, sys, collections, re
@@ -28,7 +28,7 @@ for k, c in agg.items():
     rows.append((sum(c["GRBM_GUI_ACTIVE"]) if c.get("GRBM_GUI_ACTIVE") else 0, k, len(c["GRBM_GUI_ACTIVE"]), occ, m("SQ_INSTS_MFMA"), m("SQ_VALU_MFMA_BUSY_CYCLES"), gui,
                  m("SQ_WAIT_INST_ANY") / wc, m("SQ_WAIT_ANY") / wc, m("SQ_ACTIVE_INST_ANY") / wc))
 with open(f"{out}/{tag}_mfma.md", "w") as f:
-    f.write(f"# MFMA-pipe occupancy per kernel inside the benchmark step ({tag}): rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES ... GRBM_GUI_ACTIVE -- python bench.py --no-overlap --no-graph {args}\n\n")
+    f.write(f"# MFMA-pipe occupancy per kernel inside the benchmark step ({tag}): rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES ... GRBM_GUI_ACTIVE -- python bench.py --full --no-overlap --no-graph {args}\n\n")
     f.write("One counter pass (no other trace domain), one stream, per-dispatch means.  occupancy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs);\n"
             "x effective clock / 2.4 GHz = fraction of the 2.5 PF/s peak (random data clocks ~1.8-2.0 GHz).  wave-cycle shares: issue-stalled / parked at waitcnt or barrier / issuing.\n\n")
     f.write("| kernel | dispatches | MFMA occupancy | SQ_INSTS_MFMA | MFMA_BUSY cycles | GUI_ACTIVE (sum of 8 XCDs) | WAIT_INST | WAIT_ANY | ACTIVE_INST |\n|---|---:|---:|---:|---:|---:|---:|---:|---:|\n")

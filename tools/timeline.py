@@ -2,7 +2,7 @@
 launches of a once-per-step marker kernel) in start order -> CSV (t_start_us, dur_us, gap_us since the latest end of anything before it,
 stream / queue id, short kernel name).  For the latency analysis of the launch-bound parts (mask-selection head, Llama small kernels).
 usage: python tools/timeline.py <results.db> [marker-substring=embed_splice] [steps-back=1] > step.csv
-steps-back: 1 = the last complete step, n = the n-th last (bench.py ends with eager single-stream profiling steps: go back past them to see a
+steps-back: 1 = the last complete step, n = the n-th last (bench.py --full ends with eager single-stream profiling steps: go back past them to see a
 hipGraph replay)."""
 import re
 import sqlite3
