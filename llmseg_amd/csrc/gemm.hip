@@ -7,6 +7,7 @@
 // epilogue, which bounces through LDS so that stores and residual loads are whole 128-byte lines):
 //   Q  gemm_bf16_tn_pp_kernel    256 x 256 tile, 8 waves in two groups one barrier apart ("ping-pong"), half-tile LDS-DMA ring
 //                                (buffer_load ... lds) with counted vmcnt, v_mfma_f32_16x16x32_bf16, one workgroup per CU.  Used when the tile count fills whole rounds of the CUs.
+//                                Q2 / T: its 128 x 256 and (K-slices only) 160 x 256 forms, two phases per K-tile over a three-buffer ring.
 //   G  gemm_bf16_tn_glds_kernel  128 x 128 tile, 4 waves, one LDS buffer filled by LDS-DMA, 4 workgroups per CU hide each other's
 //                                latency.  Used for everything else with K % 64 == 0.
 //   R  gemm_bf16_tn_kernel       128 x 128 tile, global -> VGPR -> LDS staging (double-buffered); any K % 8 == 0, zero-filled K
@@ -1098,6 +1099,169 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp2_kernel(GemmP p) {
   else epilogue_lds<OUT_F32, MI>(p, Acc16<MI>{acc}, smem, wave, m0, n0, wm, wn, lane, bz);
 }
 
+// ---- variant T: 160 x 256 tile, the two-phase / three-buffer ring of Q2, K-slice form only (fp32 slab out) -----------------------------------------
+// The 638-row Llama products (o, down and the dX products at 2 images per micro-step) run K-sliced on Q2: 5 x 16 tiles x 3 slices = 240 workgroups
+// on 256 CUs, and at 128 rows the LDS-DMA fill of a K-tile outlasts its MFMAs.  Here 4 x 160 = 640 rows cover M = 638, 4 x 16 tiles x 4 slices is
+// one workgroup per CU, and a K-tile moves 52 KiB for 5.24 MFLOP instead of 48 KiB for 4.19 (-16 % bytes per flop).
+//   waves 2 x 4, each 80 x 64 = 5 x 4 blocks of v_mfma_f32_16x16x32_bf16 (acc[nb][mb], the same MFMA and per-block K-step order as Q2, so at the
+//   same slice count the slabs equal Q2's bit for bit); A0 = blocks 0-1 of both wave rows (read in phase A with W0 + W1), A1 = blocks 2-4 (phase B)
+//   LDS: 3 buffers of (160 + 256) x 128 B = 156 KiB; the epilogue's per-wave 32 x 64 fp32 staging (64 KiB) aliases them after the re-join
+//   DMA pieces (8 rows x 128 B = one wave-instruction) per K-tile: A0 8, W0 16, W1 16, A1 12 -- every wave issues 1 + 2 + 2 + 1, waves with wn < 2 one
+//   more A1 piece (wave-uniform: 7 or 6 per K-tile), so the counted wait of phase B is vmcnt(7) / vmcnt(6) by a scalar branch.
+//   The ring's ordering rules are Q2's: tile t + 2 goes into the buffer tile t - 1 was read from, A0 + W0 in phase A, W1 + A1 in phase B (each region
+//   >= 2 phases after its last read), and phase B's wait retires tile t + 1 before the barrier that precedes its first reads.
+// Split-K only (p.kt_total > 0, no extension tile: the dispatch runs the extension product as a slab of its own), K % 64 == 0, >= 2 K-tiles per slice.
+constexpr int T160_BM = 160;
+#define T160_BL(rs, dst, voff, tt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(dst), 16, voff, (int)((tt) * (BK * 2)), 0, 0)
+#define T160_ISSUE_A0(tt, base) T160_BL(rsrc_a, (base) + a_lds0, a_off0, tt)
+#define T160_ISSUE_A1(tt, base)                                       \
+  do {                                                                \
+    T160_BL(rsrc_a, (base) + a_lds1[0], a_off1[0], tt);               \
+    if (two) T160_BL(rsrc_a, (base) + a_lds1[1], a_off1[1], tt);      \
+  } while (0)
+#define T160_ISSUE_W(h, tt, base)                                     \
+  do {                                                                \
+    T160_BL(rsrc_w, (base) + w_lds[h][0], w_off[h][0], tt);           \
+    T160_BL(rsrc_w, (base) + w_lds[h][1], w_off[h][1], tt);           \
+  } while (0)
+#define T160_VM_TILE do { if (two) PP_VMI(7); else PP_VMI(6); } while (0)    /* one whole K-tile of this wave may stay in flight */
+#define T160_READ_A(cnt, mb0, base)                                                                                           \
+  _Pragma("unroll") for (int mb = 0; mb < (cnt); ++mb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                     \
+      af[mb][ks] = *reinterpret_cast<const bf16x8_t*>((base) + lds_off(wm * 80 + ((mb0) + mb) * 16 + frow, ks * 4 + fq))
+#define T160_MMA(wfx, nb0, cnt, mb0)                                                                                          \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                         \
+      _Pragma("unroll") for (int mb = 0; mb < (cnt); ++mb)                                                                    \
+          acc[(nb0) + nb][(mb0) + mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfx[nb][ks], af[mb][ks], acc[(nb0) + nb][(mb0) + mb], 0, 0, 0)
+
+__global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_t160_kernel(GemmP p) {
+  constexpr int BMB = T160_BM, BNB = 256;
+  constexpr int A_BYTES = BMB * BK * 2, W_BYTES = BNB * BK * 2, BUF = A_BYTES + W_BYTES;     // 52 KiB per buffer
+  __shared__ __attribute__((aligned(16))) char smem[3 * BUF];
+  int bid = blockIdx.x;
+  const int nwg = p.tiles_m * p.tiles_n;
+  {
+    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+    const int len = q + (xcd < r ? 1 : 0);
+    const int idx = ((bid >> 3) + xcd * p.skew) % len;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  const int per_group = p.group_m * p.tiles_n;
+  const int first_m = (bid / per_group) * p.group_m;
+  const int gsz = min(p.tiles_m - first_m, p.group_m);
+  const int m0 = (first_m + (bid % per_group) % gsz) * BMB;
+  const int n0 = ((bid % per_group) / gsz) * BNB;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const bool two = wn < 2;                                // this wave issues two A1 pieces per K-tile
+  const long b1 = blockIdx.y;                             // K-slice
+  const bf16_t* __restrict__ Ag = p.A + b1 * p.sA;
+  const bf16_t* __restrict__ Wg = p.W + b1 * p.sW;
+  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Ag + (long)m0 * p.lda), 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Wg + (long)n0 * p.ldw), 0, 0x7fffffff, 0x00020000);
+  // per-lane DMA sources: the lane's LDS slot is (row0 + lane/8, chunk lane%8), it fetches global chunk (lane%8) ^ swizzle(row) of that row; rows past
+  // the matrix edge are clamped.  A0 piece = wave; A1 pieces = wave and (wn < 2) 8 + 2 wm + wn, piece j of A1 = rows 80 (j / 6) + 32 + 8 (j % 6)
+  auto a_src = [&](int ra0) { const int ra = ra0 + (lane >> 3); return (int)(((long)min(ra, p.M - 1 - m0) * p.lda + (((lane & 7) ^ ((ra >> 1) & 7)) << 3)) * 2); };
+  const int ra_a0 = wm * 80 + wn * 8;
+  const int j1 = 8 + 2 * wm + (wn & 1);
+  const int ra_a1[2] = {(wave / 6) * 80 + 32 + (wave % 6) * 8, (j1 / 6) * 80 + 32 + (j1 % 6) * 8};
+  const int a_lds0 = ra_a0 * 128, a_off0 = a_src(ra_a0);
+  const int a_lds1[2] = {ra_a1[0] * 128, ra_a1[1] * 128};
+  const int a_off1[2] = {a_src(ra_a1[0]), a_src(ra_a1[1])};
+  int w_off[2][2], w_lds[2][2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int rw0 = PP_WROW0(h, i), rw = rw0 + (lane >> 3);
+      w_lds[h][i] = A_BYTES + rw0 * 128;
+      w_off[h][i] = (int)(((long)min(rw, p.N - 1 - n0) * p.ldw + (((lane & 7) ^ ((rw >> 1) & 7)) << 3)) * 2);
+    }
+  }
+  int nt = p.K / BK;
+  nt = min(nt, p.kt_total - (int)b1 * nt);               // the last slice may be shorter
+
+  f32x4_t acc[4][5];
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+    for (int mb = 0; mb < 5; ++mb) acc[nb][mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  bf16x8_t af[3][2], wf0[2][2], wf1[2][2];
+  const int frow = lane & 15, fq = lane >> 4;
+  const int wrow0 = wn * 64, wrow1 = wrow0 + 32;
+
+  char* cur = smem;               // K-tile t
+  char* nxt = smem + BUF;         // K-tile t + 1
+  char* nn = smem + 2 * BUF;      // K-tile t + 2 (= the buffer K-tile t - 1 was read from)
+  // prologue: K-tiles 0 and 1 whole; K-tile 0 must have landed before the first barrier
+  T160_ISSUE_A0(0, cur); T160_ISSUE_W(0, 0, cur); T160_ISSUE_W(1, 0, cur); T160_ISSUE_A1(0, cur);
+  T160_ISSUE_A0(1, nxt); T160_ISSUE_W(0, 1, nxt); T160_ISSUE_W(1, 1, nxt); T160_ISSUE_A1(1, nxt);
+  T160_VM_TILE;
+  __builtin_amdgcn_s_barrier();
+  if (wm == 1) __builtin_amdgcn_s_barrier();            // the stagger
+  __builtin_amdgcn_sched_barrier(0);
+
+#define T160_RD_A P16_READ_W(wf0, 0, cur); P16_READ_W(wf1, 1, cur); T160_READ_A(2, 0, cur)
+#define T160_RD_B T160_READ_A(3, 2, cur)
+#define T160_MMA_A T160_MMA(wf0, 0, 2, 0); T160_MMA(wf1, 2, 2, 0)
+#define T160_MMA_B T160_MMA(wf1, 2, 3, 2); T160_MMA(wf0, 0, 3, 2)
+  int t = 0;
+  for (; t < nt - 2; ++t) {
+    PP_PHASE(T160_RD_A, T160_ISSUE_A0(t + 2, nn); T160_ISSUE_W(0, t + 2, nn), PP_NOP, T160_MMA_A);
+    PP_PHASE(T160_RD_B, T160_ISSUE_W(1, t + 2, nn); T160_ISSUE_A1(t + 2, nn), T160_VM_TILE, T160_MMA_B);
+    char* const tmp = cur; cur = nxt; nxt = nn; nn = tmp;
+  }
+  // K-tile nt - 2: nothing left to issue, the queue drains (K-tile nt - 1 complete before its phase A)
+  PP_PHASE(T160_RD_A, PP_NOP, PP_NOP, T160_MMA_A);
+  PP_PHASE(T160_RD_B, PP_NOP, PP_VMI(0), T160_MMA_B);
+  cur = nxt;
+  PP_PHASE(T160_RD_A, PP_NOP, PP_NOP, T160_MMA_A);
+  PP_PHASE(T160_RD_B, PP_NOP, PP_NOP, T160_MMA_B);
+#undef T160_RD_A
+#undef T160_RD_B
+#undef T160_MMA_A
+#undef T160_MMA_B
+  if (wm == 0) __builtin_amdgcn_s_barrier();            // re-join: every wave's reads and DMA are retired past this point
+
+  // epilogue: slab b1 (dense [M][N] fp32, N % 4 == 0, 16-byte aligned rows), the LDS bounce of epilogue_lds in three passes of 32 / 32 / 16 rows;
+  // the stored value is epilogue_lds's fmaf(acc, alpha, 0) (alpha = 1 here: +0 for -0, as Q2 stores it)
+  float* slab = reinterpret_cast<float*>(smem) + wave * (32 * 64);
+  const int r15 = lane & 15, q4 = lane >> 4;
+  const int c = lane & 15, rsub = lane >> 4;
+  const int n = n0 + wn * 64 + c * 4;
+  const int mw = m0 + wm * 80;
+  float* cbase = reinterpret_cast<float*>(p.C) + b1 * p.sC;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int nh = i < 2 ? 2 : 1;                         // 16-row blocks in this pass
+#pragma unroll
+    for (int h = 0; h < nh; ++h)
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        const int row = h * 16 + r15, chunk = nb * 4 + q4;
+        *reinterpret_cast<float4*>(slab + row * 64 + ((chunk ^ (row & 15)) << 2)) =
+            make_float4(acc[nb][2 * i + h][0], acc[nb][2 * i + h][1], acc[nb][2 * i + h][2], acc[nb][2 * i + h][3]);
+      }
+#pragma unroll
+    for (int it = 0; it < 4 * nh; ++it) {
+      const int row = it * 4 + rsub;
+      const float4 a4 = *reinterpret_cast<const float4*>(slab + row * 64 + ((c ^ (row & 15)) << 2));
+      const int m = mw + i * 32 + row;
+      if (m >= p.M || n >= p.N) continue;
+      *reinterpret_cast<float4*>(cbase + (long)m * p.ldc + n) =
+          make_float4(fmaf(a4.x, p.alpha, 0.f), fmaf(a4.y, p.alpha, 0.f), fmaf(a4.z, p.alpha, 0.f), fmaf(a4.w, p.alpha, 0.f));
+    }
+  }
+}
+#undef T160_BL
+#undef T160_ISSUE_A0
+#undef T160_ISSUE_A1
+#undef T160_ISSUE_W
+#undef T160_VM_TILE
+#undef T160_READ_A
+#undef T160_MMA
+
 // ---- variant V: skinny GEMM, M <= 8 rows (the decode step of generation: one token per sequence) ---------------------------------
 // C[m][n] = epi(alpha * sum_k A[m][k] W[n][k]) is a WEIGHT STREAM: every W row is read once (13.2 GB per Llama-7B token), the few A
 // rows come from L1 / L2.  HBM-bound, so no MFMA and no LDS: one wave owns 4 consecutive W rows, its 64 lanes walk K in 16-byte
@@ -1443,8 +1607,10 @@ void llmseg_prof_end(hipStream_t s, double flops);
 void llmseg_prof_tag(long a, long b, long c, long d);
 
 // tuning knob (tools/gemm_bench.py): bits 0-3 kernel (0 = register staging 128x128; 2 = LDS-DMA 128x128; 3 = four-stage LDS-DMA 128x128; 8 / 9 = LDS-DMA ping-pong
-// 256x256 / 128x256; 5 (default) = cost model), bits 4-7 = XCD skew + 1, bits 8-12 = forced split-K slice count for 8 / 9.
+// 256x256 / 128x256; 10 = LDS-DMA two-phase 160x256, K-sliced only (needs a forced slice count); 5 (default) = cost model), bits 4-7 = XCD skew + 1,
+// bits 8-12 = forced split-K slice count for 8 / 9 / 10.
 static int g_gemm_variant = 5, g_gemm_skew = 13, g_gemm_split = 0, g_gemm_pp2 = getenv("LLMSEG_GEMM_PP2") ? atoi(getenv("LLMSEG_GEMM_PP2")) : 1;
+static const bool g_gemm_t160 = getenv("LLMSEG_GEMM_NO_T160") == nullptr;      // A/B switch: no 160 x 256 K-slice plans in the cost model
 static const int g_gemm_rsplit = getenv("LLMSEG_GEMM_NO_RSPLIT") ? 0 : 1;      // K-slices for the register-staging kernel (A/B switch)
 static int num_cus() {
   static int n = [] { int dev = 0, v = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v > 0 ? v : 256; }();
@@ -1464,13 +1630,17 @@ namespace {
 // kernel ~1.0 us; prologue + epilogue ~7 / 4.5 us.  The 128 x 128 kernel shares a CU between up to 4 workgroups (2.4 us per K-tile
 // each when all four are resident, latency-bound 1.3 us when alone).
 struct GemmPlan { int variant, split; double us; };
-inline double pp_cost(long M, long N, int nt, int mi, int S, long ncu, bool f32out) {
-  const long tiles = ((M + 64 * mi - 1) / (64 * mi)) * ((N + 255) / 256);
+// bm = the tile's rows: 256 / 128 / 160.  The 160 x 256 kernel competes for K-slice plans only.  Its K-tile measures ~1.3 x the 128-row one (slope of
+// the per-call time over the 638-row shapes, profiles/r07a_gemm_t160.txt), but 4 x 16 x 4 = 256 workgroups fill every CU where 5 x 16 x 3 left 16 idle,
+// and on all five N = 4096 shapes 160 x 256 x 4 slices beats 128 x 256 x 3 by 5-13 % per call: 1.13 is the price that reproduces that ordering.
+constexpr double T160_KT_US = 1.13;
+inline double pp_cost(long M, long N, int nt, int bm, int S, long ncu, bool f32out) {
+  const long tiles = ((M + bm - 1) / bm) * ((N + 255) / 256);
   const long rounds = (tiles * S + ncu - 1) / ncu;
   const int q = (nt + S - 1) / S;
   // (round 5: re-fitting these constants to the two-phase kernel from two isolated shapes -- 0.8 + 6.4 / 1.64 + 4.5 -- moved the K-slice plans of
   // the Llama N = 4096 shapes and cost 4 % at 2 images, 6 % at 24: measured and reverted, profiles/r05g_gemm_dispatch.md)
-  const double it = mi == 4 ? 1.7 : 1.0, fix = (mi == 4 ? 7.0 : 4.5) + ((S > 1 || f32out) ? 1.0 : 0.0);
+  const double it = bm == 256 ? 1.7 : bm == 160 ? T160_KT_US : 1.0, fix = (bm == 256 ? 7.0 : 4.5) + ((S > 1 || f32out) ? 1.0 : 0.0);
   // Round 5: without K-slices a partially filled last round is priced at 0.5 + 0.5 x its fill instead of a whole round -- a CU that shares the
   // fabric with fewer neighbours fetches its operands faster (measured, tools/gemm_bench.py at the 2-image shapes: 8192 x 1280 x 1280 on 160
   // workgroups of 256 x 256 takes 35 us, not 41; the whole-round price made the 128 x 256 tile win SAM proj / lin1 / q|k|v-windows, where the
@@ -1665,8 +1835,9 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
   const int nt = p.K / BK;
   const long ncu = num_cus();
   int variant = (p.K % BK == 0 && !ta && !tw) ? (force_variant >= 0 ? force_variant : g_gemm_variant) : 0;
-  if (variant != 0 && variant != 2 && variant != 3 && variant != 8 && variant != 9) variant = 5;
+  if (variant != 0 && variant != 2 && variant != 3 && variant != 8 && variant != 9 && variant != 10) variant = 5;
   if ((variant == 8 || variant == 9) && nt < (a->A2 ? 1 : 2)) variant = 2;
+  if (variant == 10 && nt < 2) variant = 2;               // (the extension product's own K = 64 launch under a forced variant 10)
   // split-K needs a dense-enough problem for the slab layout [S][M][N], 4-column alignment and room in the caller's workspace
   const bool can_split = batch == 1 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && a->workspace != nullptr &&
                          (((uintptr_t)a->workspace) & 15) == 0 && (!p.res || (p.ldr & 3) == 0);
@@ -1676,12 +1847,19 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     // auto: minimum of the cost model over {128 x 128 DMA kernel, ping-pong 256 x 256 / 128 x 256 with 1..16 K-slices}
     GemmPlan best{2, 1, glds_cost(p.M, p.N, nt, ncu) * (double)batch};
     if (nt >= (a->A2 ? 1 : 2)) {
-      for (int mi = 4; mi >= 2; mi -= 2) {
-        for (int S = 1; S <= 16; ++S) {
+      // tiles 256 x 256 (8), 128 x 256 (9) and -- K-slice plans only -- 160 x 256 (10).  Not for the fused-epilogue calls, and not for products with a
+      // residual add: the forward's residual-stream projections (o_proj, down_proj) keep the 3-slice plan, so the forward pass -- every loss and the mask
+      // head's gradients, which the full-depth parity test measures against the fp32 oracle -- computes the bits it computed before; moving its fp32
+      // partial sums from 3 to 4 groups re-draws that chaotic comparison (profiles/r06_spread_fulldepth_grads_seeds3-5.md).  The backward dX products and
+      // lm_head's dX take the new tile.
+      const bool t160 = g_gemm_t160 && !a->fx && !a->residual;
+      for (const int bm : {256, 128, 160}) {
+        if (bm == 160 && !t160) continue;
+        for (int S = bm == 160 ? 2 : 1; S <= 16; ++S) {
           if (S > 1 && (!can_split || !split_ok(nt, S) || !ws_fits(S))) continue;
-          if (S > 1 && ((p.M + 64 * mi - 1) / (64 * mi)) * ((p.N + 255) / 256) * S > ncu) break;     // slices only to fill ONE round of the CUs
-          const double us = pp_cost(p.M, p.N, nt, mi, S, ncu, a->out_f32 != 0) * (double)batch;
-          if (us < best.us * 0.97 || (us < best.us && S == 1)) best = GemmPlan{mi == 4 ? 8 : 9, S, us};
+          if (S > 1 && ((p.M + bm - 1) / bm) * ((p.N + 255) / 256) * S > ncu) break;     // slices only to fill ONE round of the CUs
+          const double us = pp_cost(p.M, p.N, nt, bm, S, ncu, a->out_f32 != 0) * (double)batch;
+          if (us < best.us * 0.97 || (us < best.us && S == 1)) best = GemmPlan{bm == 256 ? 8 : bm == 160 ? 10 : 9, S, us};
         }
       }
     }
@@ -1699,6 +1877,9 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
   } else if (variant == 8 || variant == 9) {
     split = (g_gemm_split > 1 && force_variant < 0) ? g_gemm_split : 1;
     if (split > 1) LL_CHECK(can_split && split_ok(nt, split) && ws_fits(split), "gemm: forced split-K %d not possible for this call", split);
+  } else if (variant == 10) {
+    split = g_gemm_split;
+    LL_CHECK(split > 1 && can_split && split_ok(nt, split) && ws_fits(split), "gemm: variant 10 (160 x 256, K-sliced) needs a forced split-K count >= 2 that is possible for this call (got %d)", split);
   }
   if (p.A2) {
     // C = epi(alpha * (A.W^T + A2.W2^T)), A2 [M][64], W2 [N][64]: fused as one more K-tile of the ping-pong kernel; any other
@@ -1706,7 +1887,7 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     LL_CHECK(p.W2 && batch == 1 && !ta && !tw && (p.lda2 & 7) == 0 && (p.ldw2 & 7) == 0 && p.lda2 >= 64 && p.ldw2 >= 64 &&
                  (((uintptr_t)p.A2 | (uintptr_t)p.W2) & 15) == 0, "gemm: bad extension operands (A2 [M][64], W2 [N][64], 16-byte aligned rows)");
     LL_CHECK(!a->out_f32, "gemm: extension operands need bf16 output");
-    if ((variant == 8 || variant == 9) && split > 1) {
+    if ((variant == 8 || variant == 9 || variant == 10) && split > 1) {
       // split-K: the extension product is one more fp32 slab (a K = 64 launch of its own), summed by the reduce kernel
       llmseg_gemm_args g2 = *a;
       g2.A = a->A2; g2.W = a->W2; g2.lda = a->lda2; g2.ldw = a->ldw2; g2.K = 64; g2.A2 = g2.W2 = nullptr;
@@ -1718,7 +1899,7 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
       const int rc = llmseg_gemm_bf16(&g2, stream);
       g_norm_req.active = pend;
       if (rc != LLMSEG_OK) return rc;
-    } else if (variant != 8 && variant != 9) {
+    } else if (variant != 8 && variant != 9 && variant != 10) {
       LL_CHECK(a->act == LLMSEG_ACT_NONE && !a->gamma, "gemm: extension operands on this shape need a linear epilogue");
       llmseg_gemm_args g1 = *a, g2 = *a;
       g1.A2 = g1.W2 = nullptr;
@@ -1760,8 +1941,8 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     LL_LAUNCH_CHECK("gemm_skinny");
     return LLMSEG_OK;
   }
-  const bool pp = variant == 8 || variant == 9;
-  const int bm = variant == 8 ? 256 : 128, bn = pp ? 256 : BN;
+  const bool pp = variant == 8 || variant == 9 || variant == 10;
+  const int bm = variant == 8 ? 256 : variant == 10 ? T160_BM : 128, bn = pp ? 256 : BN;
   p.tiles_m = (p.M + bm - 1) / bm; p.tiles_n = (p.N + bn - 1) / bn;
   // ping-pong tile walk (tools/gemm_bench.py sweeps): short matrices (Llama, <= 32 row tiles) with few column tiles (N = 4096: o, down,
   // the dX products) keep all of M in one group so a W column tile is fetched once per XCD; with many column tiles (qkv, gate|up, lm_head at
@@ -1772,7 +1953,7 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
   p.group_m = group_m_env > 0 ? group_m_env : (p.tiles_m <= 32 ? ((p.tiles_n > 16 && p.tiles_m > 8 && !old_walk) ? 8 : p.tiles_m) : 4);
   hipStream_t s = (hipStream_t)stream;
   llmseg_prof_begin(s);
-  llmseg_prof_tag(p.M, p.N, p.K, (variant == 9 && g_gemm_pp2 ? 7 : variant) * 1000 + (ta ? 200 : 0) + (tw ? 100 : 0) + (p.res ? 20 : 0) + p.act * 2 + (a->out_f32 ? 1 : 0) + 40 * (batch > 1) +
+  llmseg_prof_tag(p.M, p.N, p.K, (variant == 9 && g_gemm_pp2 ? 7 : variant == 10 ? 6 : variant) * 1000 + (ta ? 200 : 0) + (tw ? 100 : 0) + (p.res ? 20 : 0) + p.act * 2 + (a->out_f32 ? 1 : 0) + 40 * (batch > 1) +
                   10000 * (split > 1 ? split : 0));
   const bool f = a->out_f32 != 0;
   // Register-staging kernel (transposed operands / K % 64 != 0) on a grid that leaves most CUs idle with a long serial K loop (a lone
@@ -1827,6 +2008,7 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     ps.c_vec = 1; ps.r_vec = 0; ps.b_vec = 1; ps.A2 = ps.W2 = nullptr;
     dim3 grid(p.tiles_m * p.tiles_n, (unsigned)split);
     if (variant == 8) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<true, false, 4>), grid, dim3(NTB), 0, s, ps);
+    else if (variant == 10) LL_LAUNCH_KERNEL(gemm_bf16_tn_t160_kernel, grid, dim3(NTB), 0, s, ps);
     else if (g_gemm_pp2 == 2) LL_LAUNCH_KERNEL((gemm_bf16_tn_lw_kernel<true>), grid, dim3(NTL), 0, s, ps);      // loader-wave form (experiment)
     else if (g_gemm_pp2) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<true, false>), grid, dim3(NTB), 0, s, ps);
     else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<true, false, 2>), grid, dim3(NTB), 0, s, ps);
