@@ -156,7 +156,7 @@ typedef struct {
   int32_t batch, heads, Nq, Nk, head_dim;
   float scale;
   int32_t causal;
-  const uint8_t* key_mask;   /* [batch][Nk] 1 = attend, or NULL */
+  const uint8_t* key_mask;   /* [batch][Nk] 1 = attend, or NULL (Nk = the capacity when nk_dev is set); a row with no key to attend gets O = 0 */
   const float* rel_h; const float* rel_w; int32_t rel_ld, grid_h, grid_w;
   const int32_t* o_row_map;
   /* Fused variant for SAM's 14x14 windows (head_dim 80): instead of rel_h/rel_w pass the bf16 tables themselves,

@@ -67,6 +67,7 @@ __device__ __forceinline__ uint32_t perm_hi(uint32_t a, uint32_t b) { return (a 
 // queries per workgroup halve the L2 -> LDS traffic and the staging work per query; the K/V tile and LDS footprint are the same).
 template <int HD, int REL, int NW = 4>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(AttnP p) {
+  const int km_ld = p.Nk;                       // key_mask is [batch][capacity]: its row stride stays the host Nk
   if (p.nk_dev) p.Nk = min(p.Nk, *p.nk_dev);   // Nk (host) = capacity, *nk_dev = keys present now
   constexpr int NT = NW * 64, BQ = NW * 32;
   constexpr int KS = HD / 16;                 // k-steps of QK^T
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(AttnP p) {
   // load inside the tile body would sit behind them in the in-order vmcnt queue, and its wait would expose the whole prefetch (22 -> see profiles).
 #define LL_PIN_V asm volatile("" : "+v"(vreg0.x), "+v"(vreg0.y), "+v"(vreg0.z), "+v"(vreg0.w), "+v"(vreg1.x), "+v"(vreg1.y), "+v"(vreg1.z), "+v"(vreg1.w), \
                                   "+v"(vreg2.x), "+v"(vreg2.y), "+v"(vreg2.z), "+v"(vreg2.w), "+v"(vreg3.x), "+v"(vreg3.y), "+v"(vreg3.z), "+v"(vreg3.w));
-#define LL_KM_LOAD(T) (p.key_mask ? (unsigned)p.key_mask[(long)b * p.Nk + min((T) * BKV + lane, p.Nk - 1)] : 1u)
+#define LL_KM_LOAD(T) (p.key_mask ? (unsigned)p.key_mask[(long)b * km_ld + min((T) * BKV + lane, p.Nk - 1)] : 1u)
   unsigned km_cur = 1u, km_nxt = 1u;
   if constexpr (DB) km_cur = LL_KM_LOAD(0);
   LL_STAGE_LOAD(0)
@@ -342,7 +343,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(AttnP p) {
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));                                                                         \
     const float m_new = fmaxf(m_run, mx);                                                                           \
     const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);                                     \
-    const float nmc = -m_new * p.scale_log2;                                                                        \
+    /* no valid key yet (m_new == NEG): -NEG * scale_log2 alone would leave the fp32 rounding error of NEG * scale_log2 (~1e21), */ \
+    /* exp2 of which is 0 or inf -- NaN for a fully masked row; with 0 every masked p is exp2(NEG * scale_log2) = 0 */ \
+    const float nmc = m_new == NEG ? 0.f : -m_new * p.scale_log2;                                                   \
     const bool moved = m_new != m_run;                                                                              \
     m_run = m_new;                                                                                                  \
     float lsum = 0.f;                                                                                               \
@@ -412,8 +415,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(AttnP p) {
 
   // ---- normalise and store: lane holds O[q][d..d+3] groups ------------------------------------------------------------
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.f / l_tot;
-  if (p.lse && half == 0 && q < p.Nq) p.lse[((long)b * p.heads + h) * p.Nq + q] = fmaf(m_run, p.scale_log2, __builtin_amdgcn_logf(l_tot));
+  // a row without any key to attend (fully masked sequence): O = 0 and a finite lse (NEG * scale_log2; the backward masks every P of it)
+  const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+  if (p.lse && half == 0 && q < p.Nq) p.lse[((long)b * p.heads + h) * p.Nq + q] = fmaf(m_run, p.scale_log2, __builtin_amdgcn_logf(l_tot > 0.f ? l_tot : 1.f));
   if (q < p.Nq) {
     bf16_t* orow;
     bool skip = false;
