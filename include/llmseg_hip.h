@@ -130,8 +130,10 @@ enum { LLMSEG_FX_NONE = 0, LLMSEG_FX_ROPE = 1, LLMSEG_FX_SWIGLU = 2, LLMSEG_FX_S
 int llmseg_gemm_bf16(const llmseg_gemm_args* args, void* stream);
 /* tuning knob (results are identical up to fp32 summation order of split-K; only speed differs):
  * bits 0-3: GEMM kernel for K % 64 == 0 shapes: 0 = register staging 128x128, 2 = LDS-DMA 128x128, 8 = LDS-DMA 256x256 ping-pong,
- *           9 = LDS-DMA 128x256 ping-pong, 5 = auto [default: a cost model picks kernel and split count];
- * bits 4-7: XCD skew + 1 (0 = keep); bits 8-12: forced split-K slice count for variants 8 / 9 (0 = 1 slice). */
+ *           9 = LDS-DMA 128x256 ping-pong, 10 = LDS-DMA 160x256 ping-pong (K-sliced only: needs a slice count >= 2 in bits 8-12, the call fails
+ *           otherwise), 5 = auto [default: a cost model picks kernel and split count]; any other value = 5;
+ * bits 4-7: XCD skew + 1 (0 = keep); bits 8-12: forced split-K slice count for variants 8 / 9 / 10 (0 = 1 slice);
+ * nothing sits above bit 12: higher bits are ignored. */
 int llmseg_gemm_set_variant(int variant);
 
 /* ---- fused attention forward -----------------------------------------------------------------

@@ -2,23 +2,27 @@
 //
 // Replaces every nn.Linear / 1x1-conv / patch-embed on the LLM-Seg hot path (see include/llmseg_hip.h).
 //
-// Three kernels, one epilogue (the MFMA "A" operand is the WEIGHT fragment and the "B" operand the ACTIVATION fragment, so a
+// Five tile kernels in three families, one epilogue (the MFMA "A" operand is the WEIGHT fragment and the "B" operand the ACTIVATION fragment, so a
 // lane ends up holding 4 consecutive output columns of one output row: bias / activation / LayerScale / residual fuse into the
 // epilogue, which bounces through LDS so that stores and residual loads are whole 128-byte lines):
 //   Q  gemm_bf16_tn_pp_kernel    256 x 256 tile, 8 waves in two groups one barrier apart ("ping-pong"), half-tile LDS-DMA ring
 //                                (buffer_load ... lds) with counted vmcnt, v_mfma_f32_16x16x32_bf16, one workgroup per CU.  Used when the tile count fills whole rounds of the CUs.
-//                                Q2 / T: its 128 x 256 and (K-slices only) 160 x 256 forms, two phases per K-tile over a three-buffer ring.
+//      gemm_bf16_tn_pp2_kernel   Q2: the 128 x 256 tile for short matrices, two phases per K-tile over a three-buffer ring.
+//      gemm_bf16_tn_t160_kernel  T: the 160 x 256 form of Q2, K-slices only (fp32 slabs).
 //   G  gemm_bf16_tn_glds_kernel  128 x 128 tile, 4 waves, one LDS buffer filled by LDS-DMA, 4 workgroups per CU hide each other's
 //                                latency.  Used for everything else with K % 64 == 0.
 //   R  gemm_bf16_tn_kernel       128 x 128 tile, global -> VGPR -> LDS staging (double-buffered); any K % 8 == 0, zero-filled K
 //                                tail, and the transposed-operand layouts of the backward pass.
+// Beside them gemm_skinny_kernel (V: M <= 8 rows, a weight stream without MFMA) and the reduce launches of K-sliced products (splitk_reduce*).
 // LDS-DMA (global_load_lds_dwordx4) writes LDS linearly (wave-uniform base + lane*16), so the XOR swizzle that makes the
 // ds_read_b128 fragment loads conflict-free on gfx950's 16-lane service groups is applied to the per-lane SOURCE address
 // (lane -> LDS slot (row, cpos) -> global chunk cpos ^ ((row>>1)&7) of that row; the 8 lanes of a row still read one 128-byte
 // line).  Workgroup ids are remapped so that each of the 8 XCDs (private L2s) walks a contiguous, M-grouped range of tiles.
 // Kernels tried and dropped (numbers in DESIGN.md): 256 x 128 LDS-DMA tiles, a lock-step 256 x 256 two-stage kernel, a 4-stage
 // BK = 32 ring, a persistent ping-pong with the next tile's DMA issued before the epilogue, K-half ping-pong phases, a 4-wave
-// 128 x 128-per-wave kernel with in-wave fragment prefetch (LDS-DMA issue from the MFMA wave costs ~170 cycles per instruction).
+// 128 x 128-per-wave kernel with in-wave fragment prefetch (LDS-DMA issue from the MFMA wave costs ~170 cycles per instruction),
+// a four-stage 128 x 128 LDS-DMA ring for the one-workgroup-per-CU shapes ("G4", knob value 3), the 128 x 256 tile with dedicated loader
+// waves, and the four-phase form of the 128 x 256 tile that Q2 replaced.
 #include <algorithm>
 #include <cstdlib>
 #include "common.h"
@@ -48,7 +52,6 @@ struct GemmP {
   const bf16_t* a_norm_w; float a_norm_eps; int a_swiglu;     // skinny route: transform of the A rows while they are loaded (decode-step fusions)
   // fused Llama-layer epilogues of the 128 x 256 two-phase kernel (llmseg_gemm_args.fx, round 6): see epilogue_fx
   int fx, fx_T, fx_cols, fx_I; const float* fx_cos; const float* fx_sin; bf16_t* fx_out; const bf16_t* fx_in; long fx_ld;
-  int ablate;                // loader-wave experiment only (LLMSEG_LW_ABLATE; results are garbage): bit 0 = no MFMAs, bit 1 = no fragment reads, bit 2 = no DMA after the prologue, bit 3 = no per-K-tile barrier
 };
 
 // exact-erf GELU on a pair (packed fp32 VALU: v_pk_fma / v_pk_mul).  Same Abramowitz-Stegun 7.1.26 erf as apply_act, rearranged:
@@ -535,12 +538,12 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_tn_kernel(GemmP p) {
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
-template <bool OUT_F32, int MI, int NBUF>
-__global__ __launch_bounds__(NT, NBUF == 2 ? (MI == 4 ? 1 : 2) : (MI == 4 ? 2 : 4)) void gemm_bf16_tn_glds_kernel(GemmP p) {
-  constexpr int BM = 64 * MI;
-  constexpr int A_BYTES = BM * BK * 2, W_BYTES = BN * BK * 2, BUF = A_BYTES + W_BYTES;
+template <bool OUT_F32>
+__global__ __launch_bounds__(NT, 4) void gemm_bf16_tn_glds_kernel(GemmP p) {
+  constexpr int MI = 2, BM = 128;
+  constexpr int A_BYTES = BM * BK * 2, W_BYTES = BN * BK * 2;
   constexpr int A_DMA = BM / 32, W_DMA = BN / 32;              // 1-KiB DMA instructions per wave per tile
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF];
+  __shared__ __attribute__((aligned(16))) char smem[A_BYTES + W_BYTES];
   const TileXY tc = tile_of<BM>(p, blockIdx.x);
   const int m0 = tc.m0, n0 = tc.n0;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -566,234 +569,40 @@ __global__ __launch_bounds__(NT, NBUF == 2 ? (MI == 4 ? 1 : 2) : (MI == 4 ? 2 : 
   }
   const int nt = p.K / BK;
 
-  auto issue = [&](int t, int buf) {
-    char* base = smem + buf * BUF;
+  auto issue = [&](int t) {
 #pragma unroll
     for (int i = 0; i < W_DMA; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(w_src[i] + (long)t * BK), (lds_ptr_t)(base + A_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(w_src[i] + (long)t * BK), (lds_ptr_t)(smem + A_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
 #pragma unroll
     for (int i = 0; i < A_DMA; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(a_src[i] + (long)t * BK), (lds_ptr_t)(base + (i * 4 + wave) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(a_src[i] + (long)t * BK), (lds_ptr_t)(smem + (i * 4 + wave) * 1024), 16, 0, 0);
   };
 
   f32x16_t acc[2][MI];
   zero_acc<MI>(acc);
   const int frow = lane & 31, fhalf = lane >> 5;
 
-  if (NBUF == 2) {
-    issue(0, 0);
-    __syncthreads();                       // hipcc drains the DMA (vmcnt(0)) ahead of the barrier
-    for (int t = 0; t < nt; ++t) {
-      if (t + 1 < nt) issue(t + 1, (t + 1) & 1);
-      const char* abase = smem + (t & 1) * BUF;
-      mma_slab<MI>(abase, abase + A_BYTES, wm, wn, frow, fhalf, acc);
-      __syncthreads();
-    }
-  } else {
-    for (int t = 0; t < nt; ++t) {
-      issue(t, 0);
-      __syncthreads();
-      mma_slab<MI>(smem, smem + A_BYTES, wm, wn, frow, fhalf, acc);
-      __syncthreads();
-    }
+  for (int t = 0; t < nt; ++t) {
+    issue(t);
+    __syncthreads();                         // hipcc drains the DMA (vmcnt(0)) ahead of the barrier
+    mma_slab<MI>(smem, smem + A_BYTES, wm, wn, frow, fhalf, acc);
+    __syncthreads();
   }
   epilogue_lds<OUT_F32, MI>(p, Acc32<MI>{acc}, smem, wave, m0, n0, wm, wn, lane, bz);
 }
-
-
-// ---- variant G4 (round 6): 128 x 128 tile, 4 waves, FOUR-stage LDS-DMA ring with counted waits ---------------------------------------------
-// For the products that put at most one workgroup on a CU (CLIP at two sequences: M = 514; the mask-selection head: M = C K = 512, N = 256 ... 2048):
-// there the 128 x 128 kernel above has nothing to hide its fetch latency with (its one or two buffers wait for every K-tile: 16.6-17.3 us on
-// 514 x 3072 x 1024 whichever kernel ran it, profiles/r04g_small_gemm_variants.txt).  Here THREE K-tiles (96 KiB) are in flight while the fourth
-// stage is computed: iteration t = { s_waitcnt vmcnt(stages still allowed in flight) | s_barrier | issue K-tile t + 3 into the buffer iteration
-// t - 1 read (every wave has passed the barrier, so every wave has finished reading it) | 16 MFMAs on stage t }.  Same lane -> (row, chunk) DMA
-// mapping, swizzle and MFMA order as the kernel above: identical bits.  K % 64 == 0; 128 KiB of LDS, one workgroup per CU.
-#define G4_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-template <bool OUT_F32>
-__global__ __launch_bounds__(NT, 1) void gemm_bf16_tn_g4_kernel(GemmP p) {
-  constexpr int MI = 2, BM = 128, NS = 4;
-  constexpr int A_BYTES = BM * BK * 2, BUF = A_BYTES + BN * BK * 2;          // 16 KiB + 16 KiB per stage
-  __shared__ __attribute__((aligned(16))) char smem[NS * BUF];
-  const TileXY tc = tile_of<BM>(p, blockIdx.x);
-  const int m0 = tc.m0, n0 = tc.n0;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const long b1 = blockIdx.y % p.batch1, b2 = blockIdx.y / p.batch1;
-  const long bz = b1 * p.sC + b2 * p.sC2;
-  const bf16_t* __restrict__ Ag = p.A + b1 * p.sA + b2 * p.sA2;
-  const bf16_t* __restrict__ Wg = p.W + b1 * p.sW + b2 * p.sW2;
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Ag + (long)m0 * p.lda), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Wg + (long)n0 * p.ldw), 0, 0x7fffffff, 0x00020000);
-  // DMA instruction i of this wave fills LDS rows (i*4 + wave)*8 .. +7 of an operand tile (1 KiB); per-lane byte offsets relative to the tile's first row
-  int a_off[4], w_off[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (i * 4 + wave) * 8 + (lane >> 3);
-    const int sw = ((lane & 7) ^ ((row >> 1) & 7)) << 3;
-    a_off[i] = (int)(((long)min(row, p.M - 1 - m0) * p.lda + sw) * 2);
-    w_off[i] = (int)(((long)min(row, p.N - 1 - n0) * p.ldw + sw) * 2);
-  }
-  const int nt = p.K / BK;
-  auto issue = [&](int t, int st) {
-    char* base = smem + st * BUF;
-    const int koff = t * (BK * 2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr_t)(base + A_BYTES + (i * 4 + wave) * 1024), 16, w_off[i], koff, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_ptr_t)(base + (i * 4 + wave) * 1024), 16, a_off[i], koff, 0, 0);
-  };
-  f32x16_t acc[2][MI];
-  zero_acc<MI>(acc);
-  const int frow = lane & 31, fhalf = lane >> 5;
-  issue(0, 0);
-  if (nt > 1) issue(1, 1);
-  if (nt > 2) issue(2, 2);
-  for (int t = 0; t < nt; ++t) {
-    const int ahead = min(nt - 1 - t, 2);            // K-tiles issued beyond t: 8 DMA instructions of this wave each
-    if (ahead == 2) G4_VM(16); else if (ahead == 1) G4_VM(8); else G4_VM(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (t + 3 < nt) issue(t + 3, (t + 3) & 3);
-    const char* abase = smem + (t & 3) * BUF;
-    mma_slab<MI>(abase, abase + A_BYTES, wm, wn, frow, fhalf, acc);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  __syncthreads();                                   // the epilogue's slabs alias stage 0
-  epilogue_lds<OUT_F32, MI>(p, Acc32<MI>{acc}, smem, wave, m0, n0, wm, wn, lane, bz);
-}
-
-// ---- variant Q-LW (round 6 experiment): the 128 x 256 tile with DEDICATED LOADER WAVES --------------------------------------------------------------
-// Hypothesis: at M = 638 the 128 x 256 tile is bound neither by the fabric (operands mostly L2 hits: a W tile is shared by the five row tiles of
-// an XCD) nor by the vector-memory path (48 KiB per K-tile = 0.75 of its 64 B/clk at full MFMA rate) but by the ISSUE cost of the LDS-DMA instructions inside
-// the waves that also issue the MFMAs: a `buffer_load ... lds` piece stalls its wave for 60-185 cycles (MI355X_MICROARCH.md), six of them per wave and K-tile
-// against 32 MFMAs (~512 cycles).  Here 8 consumer waves (2 per SIMD; the wave tiling, fragment reads, MFMA order and epilogue of the ping-pong kernels: same
-// bits) never touch global memory; 4 loader waves (one per SIMD) issue all 48 pieces of a K-tile, two K-tiles ahead, into a three-stage LDS ring.
-// ONE workgroup barrier per K-tile:  loader: s_waitcnt vmcnt(tile t landed) | barrier | issue tile t + 2 (into the stage tile t - 1 was read from: every
-// consumer has passed this barrier, so it has finished tile t - 1);  consumer: barrier | 16 fragment reads + 32 MFMAs on tile t.
-constexpr int NTL = 768;
-template <bool OUT_F32>
-__global__ __launch_bounds__(NTL, 1) void gemm_bf16_tn_lw_kernel(GemmP p) {
-  constexpr int MI = 2, BMB = 128, BNB = 256, NS = 3;
-  constexpr int A_BYTES = BMB * BK * 2, W_BYTES = BNB * BK * 2, BUF = A_BYTES + W_BYTES;      // 16 + 32 KiB per stage, 144 KiB in all
-  __shared__ __attribute__((aligned(16))) char smem[NS * BUF];
-  int bid = blockIdx.x;
-  const int nwg = p.tiles_m * p.tiles_n;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int len = q + (xcd < r ? 1 : 0);
-    const int idx = ((bid >> 3) + xcd * p.skew) % len;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int per_group = p.group_m * p.tiles_n;
-  const int first_m = (bid / per_group) * p.group_m;
-  const int gsz = min(p.tiles_m - first_m, p.group_m);
-  const int m0 = (first_m + (bid % per_group) % gsz) * BMB;
-  const int n0 = ((bid % per_group) / gsz) * BNB;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long b1 = blockIdx.y % p.batch1, b2 = blockIdx.y / p.batch1;
-  const long bz = b1 * p.sC + b2 * p.sC2;
-  int nt = p.K / BK;
-  if (p.kt_total > 0) nt = min(nt, p.kt_total - (int)b1 * nt);                                 // split-K: the last slice may be shorter
-
-  if (wave >= 8) {
-    // ------------------------------------------------------------------ loader wave l: A pieces l, l + 4, .. (4 of 16), W pieces l, l + 4, .. (8 of 32)
-    const int l = wave - 8;
-    const bf16_t* __restrict__ Ag = p.A + b1 * p.sA + b2 * p.sA2;
-    const bf16_t* __restrict__ Wg = p.W + b1 * p.sW + b2 * p.sW2;
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Ag + (long)m0 * p.lda), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Wg + (long)n0 * p.ldw), 0, 0x7fffffff, 0x00020000);
-    int a_off[4], w_off[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = (l + 4 * j) * 8 + (lane >> 3);
-      a_off[j] = (int)(((long)min(row, p.M - 1 - m0) * p.lda + (((lane & 7) ^ ((row >> 1) & 7)) << 3)) * 2);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int row = (l + 4 * j) * 8 + (lane >> 3);
-      w_off[j] = (int)(((long)min(row, p.N - 1 - n0) * p.ldw + (((lane & 7) ^ ((row >> 1) & 7)) << 3)) * 2);
-    }
-    auto issue = [&](int t, int st) {
-      char* base = smem + st * BUF + l * 1024;
-      const int koff = t * (BK * 2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr_t)(base + A_BYTES + j * 4096), 16, w_off[j], koff, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_ptr_t)(base + j * 4096), 16, a_off[j], koff, 0, 0);
-    };
-    issue(0, 0);
-    if (nt > 1) issue(1, 1);
-    int st2 = 2;                                           // stage of tile t + 2
-    for (int t = 0; t < nt; ++t) {
-      if (t + 1 < nt) G4_VM(12); else G4_VM(0);            // tile t has landed (tile t + 1 may still be in flight)
-      __builtin_amdgcn_sched_barrier(0);
-      if (!(p.ablate & 8)) __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      if (t + 2 < nt && !(p.ablate & 4)) issue(t + 2, st2);
-      st2 = st2 == NS - 1 ? 0 : st2 + 1;
-    }
-    __builtin_amdgcn_s_barrier();                          // (the consumers' barrier ahead of the epilogue)
-    return;
-  }
-
-  // ---------------------------------------------------------------------- consumer waves: 2 x 4, each 64 x 64 of the tile
-  const int wm = wave >> 2, wn = wave & 3;
-  f32x4_t acc[4][2 * MI];
-#pragma unroll
-  for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-    for (int mb = 0; mb < 2 * MI; ++mb) acc[nb][mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  const int frow = lane & 15, fq = lane >> 4;
-  int st = 0;
-  for (int t = 0; t < nt; ++t) {
-    if (!(p.ablate & 8)) __builtin_amdgcn_s_barrier();      // (bit 3: no per-K-tile barrier -- with bits 1 + 2 the bare MFMA stream of this wave arrangement)
-    __builtin_amdgcn_sched_barrier(0);
-    const char* base = smem + ((p.ablate & 2) ? 0 : st) * BUF;
-    bf16x8_t wf[4][2], af[4][2];
-    if (!(p.ablate & 2) || t == 0) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) wf[nb][ks] = *reinterpret_cast<const bf16x8_t*>(base + A_BYTES + lds_off(wn * 64 + nb * 16 + frow, ks * 4 + fq));
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) af[mb][ks] = *reinterpret_cast<const bf16x8_t*>(base + lds_off(wm * 64 + mb * 16 + frow, ks * 4 + fq));
-      }
-    }
-    if (!(p.ablate & 1)) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-          for (int mb = 0; mb < 4; ++mb) acc[nb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nb][ks], af[mb][ks], acc[nb][mb], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) acc[nb][0][0] += __builtin_bit_cast(f32x4_t, wf[nb][0])[0] + __builtin_bit_cast(f32x4_t, af[nb][1])[1] + __builtin_bit_cast(f32x4_t, wf[nb][1])[2] + __builtin_bit_cast(f32x4_t, af[nb][0])[3];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    st = st == NS - 1 ? 0 : st + 1;
-  }
-  __builtin_amdgcn_s_barrier();                            // every consumer has finished reading LDS: the epilogue's slabs alias the stages
-  epilogue_lds<OUT_F32, MI>(p, Acc16<MI>{acc}, smem, wave, m0, n0, wm, wn, lane, bz);
-}
-
-// ---- variant Q: (64 MI) x 256 tile, 8 waves in two groups that run ONE BARRIER APART ("ping-pong") -------------------------
-// MI = 4: 256 x 256 (waves 2 x 4, each 128 x 64); MI = 2: 128 x 256 (each wave 64 x 64) for short matrices (Llama at 2 images per
-// micro-step has M = 638 rows: five 128-row tiles waste 0.3 % of the rows, three 256-row tiles 17 %).
-// Each K-tile (BK = 64) is four phases; a phase is {LDS fragment reads + one half-tile of DMA issue} | barrier | {4 MI MFMAs} |
+// ---- variant Q: 256 x 256 tile, 8 waves in two groups that run ONE BARRIER APART ("ping-pong") ----------------------------
+// Waves 2 x 4, each 128 x 64 = MI x 2 blocks of 32 x 32 with MI = 4 (the 128-row tile Q2 below shares the fragment macros with MI = 2).
+// Each K-tile (BK = 64) is four phases; a phase is {LDS fragment reads + one half-tile of DMA issue} | barrier | {16 MFMAs} |
 // barrier.  Waves wm = 1 execute one extra barrier up front, so on every SIMD the wm = 0 wave's MFMA section overlaps the
 // wm = 1 wave's read/DMA section and vice versa: the matrix pipe sees back-to-back MFMAs while the partner hides LDS latency.
-//   operands per buffer (2 buffers): A[64 MI][64], W[256][64] bf16, 128-byte rows, chunk XOR (row>>1)&7
-//   half-tiles (one DMA issue by all 8 waves: MI/2 instructions for A, 2 for W):  A0/A1 = the first / second half of BOTH wave
+//   operands per buffer (2 buffers): A[256][64], W[256][64] bf16, 128-byte rows, chunk XOR (row>>1)&7
+//   half-tiles (one DMA issue by all 8 waves: 2 instructions for A, 2 for W):  A0/A1 = the first / second half of BOTH wave
 //   rows' blocks, W0/W1 = the first / second 32 rows of every 64-row wave column block.
 //   phase:        p0                p1               p2               p3
 //   reads         W0, A0            W1               A1               -
-//   MFMAs (4 MI x v_mfma_f32_16x16x32_bf16 over 2 MI accumulators each)  W0 x A0 | W1 x A0 | W1 x A1 | W0 x A1
+//   MFMAs (16 x v_mfma_f32_16x16x32_bf16 over 8 accumulators each)  W0 x A0 | W1 x A0 | W1 x A1 | W0 x A1
 //   DMA issue     W1(t+1)           A1(t+1)          A0(t+2)          W0(t+2)          (issue sequence S[g+6] at phase g)
-//   s_waitcnt     vmcnt(MI + 4)     vmcnt(MI + 4)    -                vmcnt(MI + 4)    (retires what phase g+1 reads)
+//   s_waitcnt     vmcnt(8)          vmcnt(8)         -                vmcnt(8)         (retires what phase g+1 reads)
 // Ordering rules (MI355X_MICROARCH.md "LDS-DMA"): a half-tile is read one phase AFTER the phase whose pre-barrier vmcnt retired
 // it (both groups' waits precede a barrier the reader has passed); a slot is re-issued >= 2 phases after its last read (the
 // lagging group's reads retire one barrier later).  Four half-tiles stay in flight per workgroup.  K % 64 == 0, >= 2 K-tiles.
@@ -805,8 +614,9 @@ __global__ __launch_bounds__(NTL, 1) void gemm_bf16_tn_lw_kernel(GemmP p) {
 // otherwise leave 80 % of the CUs idle.
 #define PP_KOFF(tt) ((int)(((tt) - (EXT ? 1 : 0)) * (BK * 2)))
 #define PP_DMA_X(ptr, dst) __builtin_amdgcn_global_load_lds((gbl_ptr_t)(ptr), (lds_ptr_t)(dst), 16, 0, 0)
-// first LDS row of this wave's 8-row DMA group: A half h, instruction i (i < MI / 2); W half h, instruction i (i < 2)
-#define PP_AROW0(h, i) (MI == 4 ? ((i) * 128 + (h) * 64 + wave * 8) : ((wave >> 2) * 64 + (h) * 32 + (wave & 3) * 8))
+// first LDS row of this wave's 8-row DMA group: A half h, instruction i (256-row tile: i < 2; the 128-row tile Q2 issues one, PP2_AROW0); W half h, instruction i (i < 2)
+#define PP_AROW0(h, i) ((i) * 128 + (h) * 64 + wave * 8)
+#define PP2_AROW0(h) ((wave >> 2) * 64 + (h) * 32 + (wave & 3) * 8)
 #define PP_WROW0(h, i) (((i) * 2 + (wave >> 2)) * 64 + (h) * 32 + (wave & 3) * 8)
 // NB: the LDS address handed to the DMA builtins must not be a value-dependent expression of a template parameter (hipcc 7.2 then
 // silently drops the kernel's host stub): the per-wave LDS offsets live in the runtime tables a_lds / w_lds.
@@ -821,8 +631,9 @@ __global__ __launch_bounds__(NTL, 1) void gemm_bf16_tn_lw_kernel(GemmP p) {
 #define PP_ISSUE_A(h, tt, base)                                                  \
   do {                                                                           \
     PP_BL(rsrc_a, (base) + a_lds[h][0], a_off[h][0], tt, PP_AUX_A);                        \
-    if constexpr (MI == 4) PP_BL(rsrc_a, (base) + a_lds[h][1], a_off[h][1], tt, PP_AUX_A); \
+    PP_BL(rsrc_a, (base) + a_lds[h][1], a_off[h][1], tt, PP_AUX_A);                        \
   } while (0)
+#define PP2_ISSUE_A(h, tt, base) PP_BL(rsrc_a, (base) + a_lds[h][0], a_off[h][0], tt, PP_AUX_A)
 #define PP_ISSUE_W(h, tt, base)                                                  \
   do {                                                                           \
     PP_BL(rsrc_w, (base) + w_lds[h][0], w_off[h][0], tt, PP_AUX_W);                        \
@@ -832,18 +643,19 @@ __global__ __launch_bounds__(NTL, 1) void gemm_bf16_tn_lw_kernel(GemmP p) {
 #define PP_ISSUE_AX(h, base)                                                     \
   do {                                                                           \
     PP_DMA_X(ext_a(h, 0), (base) + a_lds[h][0]);                                 \
-    if constexpr (MI == 4) PP_DMA_X(ext_a(h, 1), (base) + a_lds[h][1]);          \
+    PP_DMA_X(ext_a(h, 1), (base) + a_lds[h][1]);                                 \
   } while (0)
+#define PP2_ISSUE_AX(h, base) PP_DMA_X(ext_a(h), (base) + a_lds[h][0])
 #define PP_ISSUE_WX(h, base)                                                     \
   do {                                                                           \
     PP_DMA_X(ext_w(h, 0), (base) + w_lds[h][0]);                                 \
     PP_DMA_X(ext_w(h, 1), (base) + w_lds[h][1]);                                 \
   } while (0)
 #define PP_VMI(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-// counted waits: FULL = four half-tiles may stay in flight (2 A + 2 W = MI + 4 instructions), then the drain ladder
-#define PP_VM_FULL do { if constexpr (MI == 4) PP_VMI(8); else PP_VMI(6); } while (0)
-#define PP_VM_WA do { if constexpr (MI == 4) PP_VMI(4); else PP_VMI(3); } while (0)     /* W + A half-tile in flight */
-#define PP_VM_A do { if constexpr (MI == 4) PP_VMI(2); else PP_VMI(1); } while (0)      /* one A half-tile in flight */
+// counted waits of the 256 x 256 kernel: FULL = four half-tiles may stay in flight (2 A + 2 W, two instructions each), then the drain ladder
+#define PP_VM_FULL PP_VMI(8)
+#define PP_VM_WA PP_VMI(4)     /* W + A half-tile in flight */
+#define PP_VM_A PP_VMI(2)      /* one A half-tile in flight */
 #define PP_VM_0 PP_VMI(0)
 #define PP_NOP ((void)0)
 #define PP_PHASE(READS, ISSUE, WAIT, MMA)               \
@@ -875,11 +687,12 @@ constexpr int NTB = 512;
       _Pragma("unroll") for (int mb = 0; mb < MI; ++mb)                                                                       \
           acc[(nb0) + nb][(mb0) + mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfx[nb][ks], af[mb][ks], acc[(nb0) + nb][(mb0) + mb], 0, 0, 0)
 
-template <bool OUT_F32, bool EXT, int MI, int FX = FX_NONE>
+template <bool OUT_F32, bool EXT, int FX = FX_NONE>
 __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp_kernel(GemmP p) {
-  constexpr int BMB = 64 * MI, BNB = 256;
+  constexpr int MI = 4;
+  constexpr int BMB = 256, BNB = 256;
   constexpr int BN_STEP = FX == FX_SWIGLU ? 128 : BNB;        // FX_SWIGLU: a tile is 128 gate columns + the 128 up columns of the same index (see epilogue_fx)
-  constexpr int A_BYTES = BMB * BK * 2, W_BYTES = BNB * BK * 2, BUF = A_BYTES + W_BYTES;     // 64 KiB (MI 4) / 48 KiB (MI 2) per buffer
+  constexpr int A_BYTES = BMB * BK * 2, W_BYTES = BNB * BK * 2, BUF = A_BYTES + W_BYTES;     // 64 KiB per buffer
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   int bid = blockIdx.x;
   const int nwg = p.tiles_m * p.tiles_n;
@@ -913,7 +726,7 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp_kernel(GemmP p) {
   for (int h = 0; h < 2; ++h) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int ra0 = i < MI / 2 ? PP_AROW0(h, i) : 0, ra = ra0 + (lane >> 3);
+      const int ra0 = PP_AROW0(h, i), ra = ra0 + (lane >> 3);
       a_lds[h][i] = ra0 * 128;
       a_off[h][i] = (int)(((long)min(ra, p.M - 1 - m0) * p.lda + (((lane & 7) ^ ((ra >> 1) & 7)) << 3)) * 2);
       // fused epilogues: a W half-tile is the set of rows the waves read as their FIRST / SECOND 32-column block (what phases p0 / p1 read), so with
@@ -936,8 +749,8 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp_kernel(GemmP p) {
     return p.W2 + (long)min(n0 + rw, p.N - 1) * p.ldw2 + (((lane & 7) ^ ((rw >> 1) & 7)) << 3);
   };
 
-  // v_mfma_f32_16x16x32_bf16: 4 MI MFMAs over 2 MI independent accumulators per phase (the 32x32x16 form alternates two, and a
-  // dependent MFMA issues only every ~42 cycles): acc[nb][mb] = C block (n = 16 nb.., m = 16 mb..), 4 x 2MI blocks of f32x4
+  // v_mfma_f32_16x16x32_bf16: 16 MFMAs over 8 independent accumulators per phase (the 32x32x16 form alternates two, and a
+  // dependent MFMA issues only every ~42 cycles): acc[nb][mb] = C block (n = 16 nb.., m = 16 mb..), 4 x 8 blocks of f32x4
   f32x4_t acc[4][2 * MI];
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
@@ -986,7 +799,7 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp_kernel(GemmP p) {
 }
 
 // ---- variant Q2: 128 x 256 tile, TWO phases per K-tile, THREE LDS buffers -------------------------------------------------------
-// The 128 x 256 form of the ping-pong kernel above spends four phases of 8 MFMAs (128 matrix-pipe cycles per wave) per K-tile; a phase's
+// A 128 x 256 tile on the four-phase schedule of the kernel above spends four phases of 8 MFMAs (128 matrix-pipe cycles per wave) per K-tile; a phase's
 // fixed cost (two barriers, the LDS-DMA issue, the exposed part of the fragment-read latency: ~130-190 cycles measured per phase on both
 // tile heights) is then as long as its MFMA burst -- 1.0 us per K-tile against 0.49 us of matrix time.  Here a K-tile is TWO phases of 16
 // MFMAs: phase A = {W0, W1} x A0 (12 fragment reads), phase B = {W1, W0} x A1 (4 reads); half as many barriers per K-tile, the same DMA
@@ -1025,13 +838,15 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp2_kernel(GemmP p) {
   const bf16_t* __restrict__ Wg = p.W + b1 * p.sW + b2 * p.sW2;
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Ag + (long)m0 * p.lda), 0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Wg + (long)n0 * p.ldw), 0, 0x7fffffff, 0x00020000);
+  // one A piece and two W pieces per half-tile: a_off[h][1] / a_lds[h][1] are never issued (they keep the shape of the 256-row kernel's tables: without the
+  // idle slot hipcc 7.2 emits one s_or_b32 of this kernel with its operands swapped, and the machine code is pinned to that of the measured builds)
   int a_off[2][2], w_off[2][2];
   int a_lds[2][2], w_lds[2][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int ra0 = i < MI / 2 ? PP_AROW0(h, i) : 0, ra = ra0 + (lane >> 3);
+      const int ra0 = i == 0 ? PP2_AROW0(h) : 0, ra = ra0 + (lane >> 3);
       a_lds[h][i] = ra0 * 128;
       a_off[h][i] = (int)(((long)min(ra, p.M - 1 - m0) * p.lda + (((lane & 7) ^ ((ra >> 1) & 7)) << 3)) * 2);
       const int rw0 = PP_WROW0(h, i), rw = rw0 + (lane >> 3);
@@ -1044,8 +859,8 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp2_kernel(GemmP p) {
   int nt_main = p.K / BK;
   if (p.kt_total > 0) nt_main = min(nt_main, p.kt_total - (int)b1 * nt_main);
   const int nt = nt_main + (EXT ? 1 : 0);
-  auto ext_a = [&](int h, int i) {
-    const int ra = PP_AROW0(h, i) + (lane >> 3);
+  auto ext_a = [&](int h) {
+    const int ra = PP2_AROW0(h) + (lane >> 3);
     return p.A2 + (long)min(m0 + ra, p.M - 1) * p.lda2 + (((lane & 7) ^ ((ra >> 1) & 7)) << 3);
   };
   auto ext_w = [&](int h, int i) {
@@ -1068,9 +883,9 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp2_kernel(GemmP p) {
   char* nxt = smem + BUF;         // K-tile t + 1
   char* nn = smem + 2 * BUF;      // K-tile t + 2 (= the buffer K-tile t - 1 was read from)
   // prologue: K-tiles 0 and 1 whole (6 + 6 DMA instructions per wave); K-tile 0 must have landed before the first barrier
-  if (EXT) { PP_ISSUE_AX(0, cur); PP_ISSUE_WX(0, cur); PP_ISSUE_WX(1, cur); PP_ISSUE_AX(1, cur); }
-  else { PP_ISSUE_A(0, 0, cur); PP_ISSUE_W(0, 0, cur); PP_ISSUE_W(1, 0, cur); PP_ISSUE_A(1, 0, cur); }
-  PP_ISSUE_A(0, 1, nxt); PP_ISSUE_W(0, 1, nxt); PP_ISSUE_W(1, 1, nxt); PP_ISSUE_A(1, 1, nxt);
+  if (EXT) { PP2_ISSUE_AX(0, cur); PP_ISSUE_WX(0, cur); PP_ISSUE_WX(1, cur); PP2_ISSUE_AX(1, cur); }
+  else { PP2_ISSUE_A(0, 0, cur); PP_ISSUE_W(0, 0, cur); PP_ISSUE_W(1, 0, cur); PP2_ISSUE_A(1, 0, cur); }
+  PP2_ISSUE_A(0, 1, nxt); PP_ISSUE_W(0, 1, nxt); PP_ISSUE_W(1, 1, nxt); PP2_ISSUE_A(1, 1, nxt);
   PP_VMI(6);
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();            // the stagger
@@ -1081,8 +896,8 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp2_kernel(GemmP p) {
 #define PP2_MMA_B P16_MMA(wf1, 2, MI); P16_MMA(wf0, 0, MI)
   int t = 0;
   for (; t < nt - 2; ++t) {
-    PP_PHASE(PP2_READ_A, PP_ISSUE_A(0, t + 2, nn); PP_ISSUE_W(0, t + 2, nn), PP_NOP, PP2_MMA_A);
-    PP_PHASE(P16_READ_A(MI, cur), PP_ISSUE_W(1, t + 2, nn); PP_ISSUE_A(1, t + 2, nn), PP_VMI(6), PP2_MMA_B);
+    PP_PHASE(PP2_READ_A, PP2_ISSUE_A(0, t + 2, nn); PP_ISSUE_W(0, t + 2, nn), PP_NOP, PP2_MMA_A);
+    PP_PHASE(P16_READ_A(MI, cur), PP_ISSUE_W(1, t + 2, nn); PP2_ISSUE_A(1, t + 2, nn), PP_VMI(6), PP2_MMA_B);
     char* const tmp = cur; cur = nxt; nxt = nn; nn = tmp;
   }
   // K-tile nt - 2: nothing left to issue, the queue drains (K-tile nt - 1 complete before its phase A)
@@ -1584,20 +1399,37 @@ __global__ __launch_bounds__(256) void splitk_reduce_delta_kernel(GemmP p, const
   }
 }
 
-// a pending second output of the call being dispatched on this thread (llmseg_gemm_args.norm_out): the K-sliced ping-pong route consumes it in its reduce launch
-struct NormReq { const bf16_t* w; bf16_t* out; long ldn; float eps; bool active, done; };
-static thread_local NormReq g_norm_req = {nullptr, nullptr, 0, 0.f, false, false};
-// a pending norm-backward tail of the call being dispatched on this thread (llmseg_gemm_args.nb_x): the K-sliced ping-pong route consumes it in its reduce launch
-struct NbReq { const llmseg_gemm_args* a; void* out; bool active, done; };
-static thread_local NbReq g_nb_req = {nullptr, nullptr, false, false};
-// a pending delta tail (llmseg_gemm_args.dl_o) of the call being dispatched on this thread
-struct DlReq { const llmseg_gemm_args* a; bool active, done; };
-static thread_local DlReq g_dl_req = {nullptr, false, false};
+// The kernel of one product.  The numeric values are those of the tuning knob (llmseg_gemm_set_variant; tests and tools pass them as integers).
+enum GemmKernel {
+  K_REG = 0,       // R: register staging 128 x 128 (any layout, any K % 8 == 0)
+  K_GLDS = 2,      // G: LDS-DMA 128 x 128
+  K_AUTO = 5,      // the cost model decides (never launched)
+  K_PP256 = 8,     // Q: ping-pong 256 x 256
+  K_PP128 = 9,     // Q2: two-phase 128 x 256
+  K_T160 = 10,     // T: two-phase 160 x 256, K-slices only
+};
+inline bool is_pp(GemmKernel k) { return k == K_PP256 || k == K_PP128 || k == K_T160; }      // the 8-wave LDS-DMA tiles, 256 columns wide, one workgroup per CU
+inline int pp_rows(GemmKernel k) { return k == K_PP256 ? 256 : k == K_T160 ? T160_BM : 128; }
+inline GemmKernel kernel_of_knob(int v) { return v == K_REG || v == K_GLDS || is_pp((GemmKernel)v) ? (GemmKernel)v : K_AUTO; }      // unknown value -> cost model
 
-template <bool OUT_F32, int MI, int NBUF>
-void launch_glds(const GemmP& p, dim3 grid, hipStream_t s) {
-  LL_LAUNCH_KERNEL((gemm_bf16_tn_glds_kernel<OUT_F32, MI, NBUF>), grid, dim3(NT), 0, s, p);
+// one launch of the 256-row or the 128-row ping-pong tile: the two kernels take the same template arguments
+template <bool OUT_F32, bool EXT, int FX = FX_NONE>
+void launch_pp(GemmKernel k, const GemmP& p, dim3 grid, hipStream_t s) {
+  if (k == K_PP256) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<OUT_F32, EXT, FX>), grid, dim3(NTB), 0, s, p);
+  else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<OUT_F32, EXT, FX>), grid, dim3(NTB), 0, s, p);
 }
+
+// The fused tail of one llmseg_gemm_bf16 call: the work the caller wants behind the product (a second output, or a pointwise pass over C), with its operands in
+// the caller's own argument struct.  The entry function fills one and hands it to gemm_dispatch, which sets `done` when the K-sliced reduce launch (NORM / NB /
+// DL) or the fused-epilogue kernel (FX) did that work; otherwise the entry function runs the launches the tail stands for.  A dispatch without a tail (the
+// extension product's own launches) fuses nothing.
+enum TailKind {
+  TAIL_NORM,       // llmseg_gemm_args.norm_out: RMSNorm(C) * norm_w
+  TAIL_NB,         // .nb_x: C = norm_bwd(product [+ LoRA term]) + nb_dres
+  TAIL_DL,         // .dl_o: delta = rowsum(dO * O) per head
+  TAIL_FX,         // .fx: RoPE / SwiGLU / SwiGLU backward in the epilogue
+};
+struct GemmTail { TailKind kind; const llmseg_gemm_args* req; bool done; };
 
 }  // namespace
 
@@ -1606,10 +1438,9 @@ void llmseg_prof_begin(hipStream_t s);
 void llmseg_prof_end(hipStream_t s, double flops);
 void llmseg_prof_tag(long a, long b, long c, long d);
 
-// tuning knob (tools/gemm_bench.py): bits 0-3 kernel (0 = register staging 128x128; 2 = LDS-DMA 128x128; 3 = four-stage LDS-DMA 128x128; 8 / 9 = LDS-DMA ping-pong
-// 256x256 / 128x256; 10 = LDS-DMA two-phase 160x256, K-sliced only (needs a forced slice count); 5 (default) = cost model), bits 4-7 = XCD skew + 1,
-// bits 8-12 = forced split-K slice count for 8 / 9 / 10.
-static int g_gemm_variant = 5, g_gemm_skew = 13, g_gemm_split = 0, g_gemm_pp2 = getenv("LLMSEG_GEMM_PP2") ? atoi(getenv("LLMSEG_GEMM_PP2")) : 1;
+// tuning knob (tools/gemm_bench.py): bits 0-3 kernel (a GemmKernel value; 10 needs a forced slice count; anything else = 5, the default = cost model),
+// bits 4-7 = XCD skew + 1, bits 8-12 = forced split-K slice count for 8 / 9 / 10.  Higher bits are ignored.
+static int g_gemm_variant = K_AUTO, g_gemm_skew = 13, g_gemm_split = 0;
 static const bool g_gemm_t160 = getenv("LLMSEG_GEMM_NO_T160") == nullptr;      // A/B switch: no 160 x 256 K-slice plans in the cost model
 static const int g_gemm_rsplit = getenv("LLMSEG_GEMM_NO_RSPLIT") ? 0 : 1;      // K-slices for the register-staging kernel (A/B switch)
 static int num_cus() {
@@ -1620,7 +1451,6 @@ extern "C" int llmseg_gemm_set_variant(int v) {
   g_gemm_variant = v & 15;
   if ((v >> 4) & 15) g_gemm_skew = ((v >> 4) & 15) - 1;
   g_gemm_split = (v >> 8) & 31;
-  g_gemm_pp2 = (v >> 13) & 3 ? ((v >> 13) & 3) - 1 : g_gemm_pp2;     // bits 13-14: 128 x 256 kernel form + 1 (1 = four phases / two buffers, 2 = two phases / three buffers, 3 = loader waves)
   return LLMSEG_OK;
 }
 
@@ -1629,7 +1459,7 @@ namespace {
 // One ping-pong workgroup owns a CU: a K-tile of the 256 x 256 kernel takes ~1.7 us (1.25 PF/s over 256 CUs), of the 128 x 256
 // kernel ~1.0 us; prologue + epilogue ~7 / 4.5 us.  The 128 x 128 kernel shares a CU between up to 4 workgroups (2.4 us per K-tile
 // each when all four are resident, latency-bound 1.3 us when alone).
-struct GemmPlan { int variant, split; double us; };
+struct GemmPlan { GemmKernel kernel; int split; double us; };
 // bm = the tile's rows: 256 / 128 / 160.  The 160 x 256 kernel competes for K-slice plans only.  Its K-tile measures ~1.3 x the 128-row one (slope of
 // the per-call time over the 638-row shapes, profiles/r07a_gemm_t160.txt), but 4 x 16 x 4 = 256 workgroups fill every CU where 5 x 16 x 3 left 16 idle,
 // and on all five N = 4096 shapes 160 x 256 x 4 slices beats 128 x 256 x 3 by 5-13 % per call: 1.13 is the price that reproduces that ordering.
@@ -1668,7 +1498,7 @@ inline bool split_ok(int nt, int S) {       // every slice needs >= 2 K-tiles (t
 }
 }  // namespace
 
-static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_variant);
+static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, GemmTail* tail);
 
 extern "C" int llmseg_norm(const void* x, const void* w, const void* b, void* y, int64_t rows, int64_t cols, int64_t ldx, int64_t ldy, float eps, int rms,
                            const int32_t* row_map, void* stream);
@@ -1677,7 +1507,6 @@ extern "C" int llmseg_rope(void* x, const float* cos, const float* sin, int64_t 
 extern "C" int llmseg_swiglu(const void* gu, void* out, int64_t rows, int64_t I, int64_t ldgu, int64_t ldo, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int llmseg_swiglu_bwd_ld(const void* gu, const void* dout, void* dgu, int64_t rows, int64_t I, int64_t ld_dout, void* stream);
 
-static thread_local bool g_fx_done = false;        // set by gemm_dispatch when the fused-epilogue kernel ran for the call being dispatched on this thread
 static const bool g_fx_off = getenv("LLMSEG_GEMM_NO_FX") != nullptr;      // A/B switch: always the GEMM + pointwise launch
 
 // llmseg_gemm_args.fx: the fused kernel where the call takes the 128 x 256 two-phase kernel in one K-slice (the Llama layer at 2 images per micro-step),
@@ -1698,11 +1527,11 @@ static int gemm_fx(const llmseg_gemm_args* a, void* stream) {
                  ((((uintptr_t)a->fx_in) | ((uintptr_t)a->C)) & 15) == 0,
              "gemm: fx swiglu_bwd needs N = I, fx_in = gate|up bf16 [M][fx_ld >= 2 I], C = d(gate|up) [M][ldc >= 2 I], 16-byte aligned rows");
   }
-  g_fx_done = false;
   llmseg_gemm_args g = *a;
   if (a->fx == LLMSEG_FX_SWIGLU_BWD) g.C = (bf16_t*)a->C + a->N;      // unfused route: d(out) lands in the up half of C's rows, llmseg_swiglu_bwd then works in place
-  const int rc = gemm_dispatch(&g, stream, -1);
-  if (rc != LLMSEG_OK || g_fx_done) return rc;
+  GemmTail tail{TAIL_FX, a, false};
+  const int rc = gemm_dispatch(&g, stream, g_fx_off ? nullptr : &tail);
+  if (rc != LLMSEG_OK || tail.done) return rc;
   if (a->fx == LLMSEG_FX_ROPE) return llmseg_rope(a->C, a->fx_cos, a->fx_sin, a->M, a->fx_T, (int32_t)(a->fx_cols / 128), 128, a->ldc, stream);
   if (a->fx == LLMSEG_FX_SWIGLU) return llmseg_swiglu(a->C, a->fx_out, a->M, a->N / 2, a->ldc, a->fx_ld, stream);
   LL_CHECK(a->fx_ld == 2 * a->N && a->ldc == 2 * a->N, "gemm: fx swiglu_bwd on this shape (two-launch route) needs dense gate|up and d(gate|up) rows");
@@ -1737,11 +1566,9 @@ static int gemm_nb(const llmseg_gemm_args* a, void* stream) {
   void* tmp = (char*)a->workspace + g.workspace_bytes;
   g.C = tmp;                                                  // the two-launch routes leave the bf16 product here; the fused tail writes a->C itself
   g.nb_x = nullptr;
-  g_nb_req = NbReq{a, a->C, !g_nb_off, false};
-  const int rc = gemm_dispatch(&g, stream, -1);
-  const bool done = g_nb_req.done;
-  g_nb_req.active = false;
-  if (rc != LLMSEG_OK || done) return rc;
+  GemmTail tail{TAIL_NB, a, false};
+  const int rc = gemm_dispatch(&g, stream, g_nb_off ? nullptr : &tail);
+  if (rc != LLMSEG_OK || tail.done) return rc;
   if (a->nb_lora_t && a->nb_lora_part) {          // the LoRA operand is still K-slice partials: finish them first (what the fused tail does in its own launch)
     const int rc0 = llmseg_lora_down_finish(a->nb_lora_part, a->nb_lora_S, (void*)a->nb_lora_t, a->nb_lora_ldt, a->M, a->nb_lora_scale, a->nb_lora_zero, a->nb_lora_w1 ? 2 : 1, stream);
     if (rc0 != LLMSEG_OK) return rc0;
@@ -1765,13 +1592,11 @@ static int gemm_dl(const llmseg_gemm_args* a, void* stream) {
                ((((uintptr_t)a->dl_o) | ((uintptr_t)a->C)) & 15) == 0,
            "gemm: dl_o needs a plain bf16 product of width heads x 128 over batch x T rows, 16-byte aligned rows");
   static const bool off = getenv("LLMSEG_GEMM_NO_DL") != nullptr;      // A/B switch
-  g_dl_req = DlReq{a, !off, false};
   llmseg_gemm_args g = *a;
   g.dl_o = nullptr;
-  const int rc = gemm_dispatch(&g, stream, -1);
-  const bool done = g_dl_req.done;
-  g_dl_req.active = false;
-  if (rc != LLMSEG_OK || done) return rc;
+  GemmTail tail{TAIL_DL, a, false};
+  const int rc = gemm_dispatch(&g, stream, off ? nullptr : &tail);
+  if (rc != LLMSEG_OK || tail.done) return rc;
   return llmseg_attn_delta128(a->dl_o, a->dl_ldo, a->C, a->ldc, a->dl_out, a->M / a->dl_T, a->dl_heads, a->dl_T, stream);
 }
 
@@ -1779,21 +1604,20 @@ extern "C" int llmseg_gemm_bf16(const llmseg_gemm_args* a, void* stream) {
   if (a && a->struct_size == sizeof(*a) && a->fx) return gemm_fx(a, stream);
   if (a && a->struct_size == sizeof(*a) && a->nb_x) return gemm_nb(a, stream);
   if (a && a->struct_size == sizeof(*a) && a->dl_o) return gemm_dl(a, stream);
-  if (!(a && a->struct_size == sizeof(*a) && a->norm_out)) return gemm_dispatch(a, stream, -1);
+  if (!(a && a->struct_size == sizeof(*a) && a->norm_out)) return gemm_dispatch(a, stream, nullptr);
   // second output RMSNorm(C) * norm_w: the K-sliced route folds it into its reduce launch, every other route gets llmseg_norm behind the product
   LL_CHECK(a->norm_w && !a->out_f32 && a->batch <= 1 && a->batch2 <= 1 && (a->N & 7) == 0 && (a->ldn & 7) == 0 && a->ldn >= a->N && (a->ldc & 7) == 0 &&
                ((((uintptr_t)a->norm_w) | ((uintptr_t)a->norm_out) | ((uintptr_t)a->C)) & 15) == 0 && !a->accumulate,
            "gemm: norm_out needs norm_w, bf16 output, batch 1, N, ldc and ldn multiples of 8, 16-byte aligned pointers");
-  g_norm_req = NormReq{(const bf16_t*)a->norm_w, (bf16_t*)a->norm_out, (long)a->ldn, a->norm_eps, true, false};
-  const int rc = gemm_dispatch(a, stream, -1);
-  const bool done = g_norm_req.done;
-  g_norm_req.active = false;
-  if (rc != LLMSEG_OK || done) return rc;
+  static const bool no_fuse = getenv("LLMSEG_GEMM_NO_NORM_FUSE") != nullptr;      // A/B switch: always the two-launch route
+  GemmTail tail{TAIL_NORM, a, false};
+  const int rc = gemm_dispatch(a, stream, no_fuse ? nullptr : &tail);
+  if (rc != LLMSEG_OK || tail.done) return rc;
   return llmseg_norm(a->C, a->norm_w, nullptr, a->norm_out, a->M, a->N, a->ldc, a->ldn, a->norm_eps, 1, nullptr, stream);
 }
 
-// force_variant >= 0: an internal caller fixes the kernel (8 / 9, one K-slice)
-static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_variant) {
+// tail: the caller's fused tail (see GemmTail), or nullptr
+static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, GemmTail* tail) {
   LL_CHECK(a && a->struct_size == sizeof(*a), "%s: ABI mismatch: caller's struct_size %u != %zu (bind against include/llmseg_hip.h version %d)",
            "gemm", a ? a->struct_size : 0u, sizeof(*a), LLMSEG_ABI_VERSION);
   LL_CHECK(a && a->A && a->W && a->C, "gemm: null pointer");
@@ -1823,7 +1647,6 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
   p.kt_total = 0; p.k_split_total = 0; p.accum = a->accumulate ? 1 : 0;
   p.fx = 0; p.fx_T = a->fx_T; p.fx_cols = (int)a->fx_cols; p.fx_I = a->fx == LLMSEG_FX_SWIGLU ? (int)(a->N / 2) : (int)a->N;
   p.fx_cos = a->fx_cos; p.fx_sin = a->fx_sin; p.fx_out = (bf16_t*)a->fx_out; p.fx_in = (const bf16_t*)a->fx_in; p.fx_ld = a->fx_ld;
-  { static const int abl = getenv("LLMSEG_LW_ABLATE") ? atoi(getenv("LLMSEG_LW_ABLATE")) : 0; p.ablate = abl; }
   // vector stores/loads need 4-element alignment of every row start; otherwise the kernel goes element-wise
   p.c_vec = ((((uintptr_t)a->C) % (4 * esz)) == 0 && (a->ldc & 3) == 0 && ((a->strideC | a->strideC2) & 3) == 0) ? 1 : 0;
   p.r_vec = (p.res && (((uintptr_t)p.res) & 7) == 0 && (p.ldr & 3) == 0 && ((a->strideC | a->strideC2) & 3) == 0) ? 1 : 0;
@@ -1834,50 +1657,41 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
   static const int group_m_env = getenv("LLMSEG_GEMM_GROUP_M") ? atoi(getenv("LLMSEG_GEMM_GROUP_M")) : 0;   // tuning override
   const int nt = p.K / BK;
   const long ncu = num_cus();
-  int variant = (p.K % BK == 0 && !ta && !tw) ? (force_variant >= 0 ? force_variant : g_gemm_variant) : 0;
-  if (variant != 0 && variant != 2 && variant != 3 && variant != 8 && variant != 9 && variant != 10) variant = 5;
-  if ((variant == 8 || variant == 9) && nt < (a->A2 ? 1 : 2)) variant = 2;
-  if (variant == 10 && nt < 2) variant = 2;               // (the extension product's own K = 64 launch under a forced variant 10)
+  // ---- the plan: kernel and K-slice count
+  GemmKernel kernel = (p.K % BK == 0 && !ta && !tw) ? kernel_of_knob(g_gemm_variant) : K_REG;
+  if ((kernel == K_PP256 || kernel == K_PP128) && nt < (a->A2 ? 1 : 2)) kernel = K_GLDS;
+  if (kernel == K_T160 && nt < 2) kernel = K_GLDS;        // (the extension product's own K = 64 launch under a forced 160 x 256 tile)
   // split-K needs a dense-enough problem for the slab layout [S][M][N], 4-column alignment and room in the caller's workspace
   const bool can_split = batch == 1 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && a->workspace != nullptr &&
                          (((uintptr_t)a->workspace) & 15) == 0 && (!p.res || (p.ldr & 3) == 0);
   auto ws_fits = [&](int S) { return (double)(S + (a->A2 ? 1 : 0)) * p.M * p.N * 4.0 <= (double)a->workspace_bytes; };   // + the extension product's slab
   int split = 1;
-  if (variant == 5) {
+  if (kernel == K_AUTO) {
     // auto: minimum of the cost model over {128 x 128 DMA kernel, ping-pong 256 x 256 / 128 x 256 with 1..16 K-slices}
-    GemmPlan best{2, 1, glds_cost(p.M, p.N, nt, ncu) * (double)batch};
+    GemmPlan best{K_GLDS, 1, glds_cost(p.M, p.N, nt, ncu) * (double)batch};
     if (nt >= (a->A2 ? 1 : 2)) {
-      // tiles 256 x 256 (8), 128 x 256 (9) and -- K-slice plans only -- 160 x 256 (10).  Not for the fused-epilogue calls, and not for products with a
+      // tiles 256 x 256, 128 x 256 and -- K-slice plans only -- 160 x 256.  Not for the fused-epilogue calls, and not for products with a
       // residual add: the forward's residual-stream projections (o_proj, down_proj) keep the 3-slice plan, so the forward pass -- every loss and the mask
       // head's gradients, which the full-depth parity test measures against the fp32 oracle -- computes the bits it computed before; moving its fp32
       // partial sums from 3 to 4 groups re-draws that chaotic comparison (profiles/r06_spread_fulldepth_grads_seeds3-5.md).  The backward dX products and
       // lm_head's dX take the new tile.
       const bool t160 = g_gemm_t160 && !a->fx && !a->residual;
-      for (const int bm : {256, 128, 160}) {
-        if (bm == 160 && !t160) continue;
-        for (int S = bm == 160 ? 2 : 1; S <= 16; ++S) {
+      for (const GemmKernel k : {K_PP256, K_PP128, K_T160}) {
+        if (k == K_T160 && !t160) continue;
+        const int bm = pp_rows(k);
+        for (int S = k == K_T160 ? 2 : 1; S <= 16; ++S) {
           if (S > 1 && (!can_split || !split_ok(nt, S) || !ws_fits(S))) continue;
           if (S > 1 && ((p.M + bm - 1) / bm) * ((p.N + 255) / 256) * S > ncu) break;     // slices only to fill ONE round of the CUs
           const double us = pp_cost(p.M, p.N, nt, bm, S, ncu, a->out_f32 != 0) * (double)batch;
-          if (us < best.us * 0.97 || (us < best.us && S == 1)) best = GemmPlan{bm == 256 ? 8 : bm == 160 ? 10 : 9, S, us};
+          if (us < best.us * 0.97 || (us < best.us && S == 1)) best = GemmPlan{k, S, us};
         }
       }
     }
-    // round 6: the four-stage 128 x 128 kernel for products that fit ONE round of the CUs (at most one workgroup per CU: nothing else hides the
-    // fetch latency there): ~0.55 us per K-tile behind a three-tile-deep DMA queue + ~4 us of first-tile latency and epilogue (tools/gemm_bench.py, GEMM_SET=clip)
-    static const int g4_env = getenv("LLMSEG_GEMM_G4") ? atoi(getenv("LLMSEG_GEMM_G4")) : 0;      // A/B switch: 1 = let the cost model pick it
-    if (g4_env && !a->A2 && nt >= 2) {
-      const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * batch;
-      if (t128 <= ncu) {
-        const double us = nt * 0.55 + 4.0;
-        if (us < best.us) best = GemmPlan{3, 1, us};
-      }
-    }
-    variant = best.variant; split = best.split;
-  } else if (variant == 8 || variant == 9) {
-    split = (g_gemm_split > 1 && force_variant < 0) ? g_gemm_split : 1;
+    kernel = best.kernel; split = best.split;
+  } else if (kernel == K_PP256 || kernel == K_PP128) {
+    split = g_gemm_split > 1 ? g_gemm_split : 1;
     if (split > 1) LL_CHECK(can_split && split_ok(nt, split) && ws_fits(split), "gemm: forced split-K %d not possible for this call", split);
-  } else if (variant == 10) {
+  } else if (kernel == K_T160) {
     split = g_gemm_split;
     LL_CHECK(split > 1 && can_split && split_ok(nt, split) && ws_fits(split), "gemm: variant 10 (160 x 256, K-sliced) needs a forced split-K count >= 2 that is possible for this call (got %d)", split);
   }
@@ -1887,29 +1701,23 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     LL_CHECK(p.W2 && batch == 1 && !ta && !tw && (p.lda2 & 7) == 0 && (p.ldw2 & 7) == 0 && p.lda2 >= 64 && p.ldw2 >= 64 &&
                  (((uintptr_t)p.A2 | (uintptr_t)p.W2) & 15) == 0, "gemm: bad extension operands (A2 [M][64], W2 [N][64], 16-byte aligned rows)");
     LL_CHECK(!a->out_f32, "gemm: extension operands need bf16 output");
-    if ((variant == 8 || variant == 9 || variant == 10) && split > 1) {
+    if (is_pp(kernel) && split > 1) {
       // split-K: the extension product is one more fp32 slab (a K = 64 launch of its own), summed by the reduce kernel
       llmseg_gemm_args g2 = *a;
       g2.A = a->A2; g2.W = a->W2; g2.lda = a->lda2; g2.ldw = a->ldw2; g2.K = 64; g2.A2 = g2.W2 = nullptr;
       g2.bias = g2.gamma = g2.residual = nullptr; g2.alpha = 1.f; g2.act = LLMSEG_ACT_NONE; g2.out_f32 = 1; g2.accumulate = 0;
       g2.C = (float*)a->workspace + (long)split * p.M * p.N; g2.ldc = p.N; g2.workspace = nullptr; g2.workspace_bytes = 0;
-      g2.norm_w = nullptr; g2.norm_out = nullptr;              // (the caller's second output belongs to the whole product, not to this slab)
-      const bool pend = g_norm_req.active;
-      g_norm_req.active = false;
-      const int rc = llmseg_gemm_bf16(&g2, stream);
-      g_norm_req.active = pend;
+      const int rc = gemm_dispatch(&g2, stream, nullptr);        // (no tail: the caller's belongs to the whole product, not to this slab)
       if (rc != LLMSEG_OK) return rc;
-    } else if (variant != 8 && variant != 9 && variant != 10) {
+    } else if (!is_pp(kernel)) {
       LL_CHECK(a->act == LLMSEG_ACT_NONE && !a->gamma, "gemm: extension operands on this shape need a linear epilogue");
       llmseg_gemm_args g1 = *a, g2 = *a;
       g1.A2 = g1.W2 = nullptr;
-      g1.norm_w = g2.norm_w = nullptr; g1.norm_out = g2.norm_out = nullptr;      // second output: after BOTH launches (the entry point's llmseg_norm)
-      g_norm_req.active = false;
-      int rc = llmseg_gemm_bf16(&g1, stream);
+      int rc = gemm_dispatch(&g1, stream, nullptr);               // no tail: the caller's work comes after BOTH launches (the entry function runs it)
       if (rc != LLMSEG_OK) return rc;
       g2.A = a->A2; g2.W = a->W2; g2.lda = a->lda2; g2.ldw = a->ldw2; g2.K = 64; g2.bias = nullptr; g2.residual = a->C; g2.ldr = a->ldc;
       g2.A2 = g2.W2 = nullptr;
-      return llmseg_gemm_bf16(&g2, stream);
+      return gemm_dispatch(&g2, stream, nullptr);
     }
   }
   p.a_norm_w = (const bf16_t*)a->a_norm_w; p.a_norm_eps = a->a_norm_eps; p.a_swiglu = a->a_swiglu;
@@ -1917,7 +1725,7 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
   LL_CHECK(!a_xform || (p.M <= 8 && !ta && !tw && batch == 1 && !p.A2 && (p.K & 7) == 0 && !(p.a_norm_w && p.a_swiglu) &&
                         (!p.a_norm_w || (((uintptr_t)p.a_norm_w) & 15) == 0) && (!p.a_swiglu || p.lda >= 2 * p.K)),
            "gemm: A-row transforms (a_norm_w / a_swiglu) are decode-step fusions of the M <= 8 route");
-  if (p.M <= 8 && !ta && !tw && batch == 1 && !p.A2 && (p.K & 7) == 0 && (g_gemm_variant == 5 || a_xform)) {
+  if (p.M <= 8 && !ta && !tw && batch == 1 && !p.A2 && (p.K & 7) == 0 && (g_gemm_variant == K_AUTO || a_xform)) {
     // skinny GEMM (decode steps, single-row head GEMMs): a weight stream, HBM-bound
     hipStream_t s = (hipStream_t)stream;
     llmseg_prof_begin(s);
@@ -1941,25 +1749,25 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     LL_LAUNCH_CHECK("gemm_skinny");
     return LLMSEG_OK;
   }
-  const bool pp = variant == 8 || variant == 9 || variant == 10;
-  const int bm = variant == 8 ? 256 : variant == 10 ? T160_BM : 128, bn = pp ? 256 : BN;
+  // ---- the launch
+  const bool pp = is_pp(kernel);
+  const int bm = pp ? pp_rows(kernel) : 128, bn = pp ? 256 : BN;
   p.tiles_m = (p.M + bm - 1) / bm; p.tiles_n = (p.N + bn - 1) / bn;
   // ping-pong tile walk (tools/gemm_bench.py sweeps): short matrices (Llama, <= 32 row tiles) with few column tiles (N = 4096: o, down,
   // the dX products) keep all of M in one group so a W column tile is fetched once per XCD; with many column tiles (qkv, gate|up, lm_head at
   // 16-24 images: 20-30 row tiles x 48-126 column tiles) an XCD's 32 concurrent tiles would be ONE column tile deep and re-stream all of A
   // (63 MB at 24 images) per column tile -- 8 row tiles per group make the concurrent set 8 x 4 (+5..8 %: qkv 1017 -> 1100, gate|up
   // 1215 -> 1300, lm_head 1234 -> 1310 TF/s at 16 images); tall ones (SAM, 384+ row tiles) walk 4 row tiles per group (+3..6 % at K = 5120)
-  static const bool old_walk = getenv("LLMSEG_GEMM_OLD_WALK") != nullptr;     // A/B switch
-  p.group_m = group_m_env > 0 ? group_m_env : (p.tiles_m <= 32 ? ((p.tiles_n > 16 && p.tiles_m > 8 && !old_walk) ? 8 : p.tiles_m) : 4);
+  p.group_m = group_m_env > 0 ? group_m_env : (p.tiles_m <= 32 ? ((p.tiles_n > 16 && p.tiles_m > 8) ? 8 : p.tiles_m) : 4);
   hipStream_t s = (hipStream_t)stream;
   llmseg_prof_begin(s);
-  llmseg_prof_tag(p.M, p.N, p.K, (variant == 9 && g_gemm_pp2 ? 7 : variant == 10 ? 6 : variant) * 1000 + (ta ? 200 : 0) + (tw ? 100 : 0) + (p.res ? 20 : 0) + p.act * 2 + (a->out_f32 ? 1 : 0) + 40 * (batch > 1) +
+  llmseg_prof_tag(p.M, p.N, p.K, (kernel == K_PP128 ? 7 : kernel == K_T160 ? 6 : (int)kernel) * 1000 + (ta ? 200 : 0) + (tw ? 100 : 0) + (p.res ? 20 : 0) + p.act * 2 + (a->out_f32 ? 1 : 0) + 40 * (batch > 1) +
                   10000 * (split > 1 ? split : 0));
   const bool f = a->out_f32 != 0;
   // Register-staging kernel (transposed operands / K % 64 != 0) on a grid that leaves most CUs idle with a long serial K loop (a lone
   // workgroup takes 1.2-3 us per K-tile, all of it exposed latency: 512 x 256 x 2048 with W stored [K][N] was 75 us on 8 workgroups):
   // K-slices as the (inner) batch index, fp32 slabs in the caller's workspace, epilogue in the reduce launch.
-  if (variant == 0 && batch2 == 1 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && a->workspace != nullptr && (((uintptr_t)a->workspace) & 15) == 0 &&
+  if (kernel == K_REG && batch2 == 1 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && a->workspace != nullptr && (((uintptr_t)a->workspace) & 15) == 0 &&
       (!p.res || ((p.ldr & 3) == 0 && batch == 1)) && ((p.sC & 3) == 0 || batch == 1) && g_gemm_rsplit) {
     const long tiles = (long)p.tiles_m * p.tiles_n * batch;
     const int ntr = (p.K + BK - 1) / BK;
@@ -1971,9 +1779,6 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     }
     if (S > 1) {
       const int q = (ntr + S - 1) / S;
-      static const bool log_it = getenv("LLMSEG_RSPLIT_LOG") != nullptr;
-      if (log_it) fprintf(stderr, "rsplit M=%d N=%d K=%d ta=%d tw=%d S=%d q=%d f32=%d acc=%d res=%d bias=%d act=%d lda=%ld ldw=%ld ldc=%ld batch=%ld alpha=%g\n", p.M, p.N, p.K,
-                          (int)ta, (int)tw, S, q, (int)f, p.accum, p.res != nullptr, p.bias != nullptr, p.act, p.lda, p.ldw, p.ldc, batch, p.alpha);
       GemmP ps = p;
       ps.K = q * BK; ps.k_split_total = p.K; ps.batch1 = S;
       ps.sA = ta ? (long)q * BK * p.lda : (long)q * BK; ps.sW = tw ? (long)q * BK * p.ldw : (long)q * BK;
@@ -2007,117 +1812,77 @@ static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, int force_vari
     ps.bias = ps.gamma = ps.res = nullptr; ps.ldr = 0; ps.alpha = 1.f; ps.act = LLMSEG_ACT_NONE; ps.accum = 0;
     ps.c_vec = 1; ps.r_vec = 0; ps.b_vec = 1; ps.A2 = ps.W2 = nullptr;
     dim3 grid(p.tiles_m * p.tiles_n, (unsigned)split);
-    if (variant == 8) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<true, false, 4>), grid, dim3(NTB), 0, s, ps);
-    else if (variant == 10) LL_LAUNCH_KERNEL(gemm_bf16_tn_t160_kernel, grid, dim3(NTB), 0, s, ps);
-    else if (g_gemm_pp2 == 2) LL_LAUNCH_KERNEL((gemm_bf16_tn_lw_kernel<true>), grid, dim3(NTL), 0, s, ps);      // loader-wave form (experiment)
-    else if (g_gemm_pp2) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<true, false>), grid, dim3(NTB), 0, s, ps);
-    else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<true, false, 2>), grid, dim3(NTB), 0, s, ps);
-    const long total4 = (long)p.M * (p.N >> 2);
-    const unsigned rg = (unsigned)std::min<long>((total4 + 255) / 256, 4096);
+    if (kernel == K_T160) LL_LAUNCH_KERNEL(gemm_bf16_tn_t160_kernel, grid, dim3(NTB), 0, s, ps);
+    else launch_pp<true, false>(kernel, ps, grid, s);
+    // the reduce launch: sums the slabs (+ the extension product's) and applies the epilogue; the caller's tail rides in it where a row kernel can do both
+    const float* slabs = (const float*)a->workspace;
+    const int S2 = split + (p.A2 ? 1 : 0);
+    const int cpt = ((p.N >> 3) + 255) / 256;                 // 8-column chunks per thread of the workgroup-per-row kernels
+    const llmseg_gemm_args* r = tail ? tail->req : nullptr;
     // the row kernel only where llmseg_norm would run its workgroup-per-row kernel on this shape (same arithmetic, same bits) and the epilogue is the plain residual add
     static const long wg_max_rows = getenv("LLMSEG_NORM_WG_MAX") ? atol(getenv("LLMSEG_NORM_WG_MAX")) : 2048;
-    static const bool no_fuse = getenv("LLMSEG_GEMM_NO_NORM_FUSE") != nullptr;      // A/B switch: always the two-launch route
-    const bool fuse_norm = g_norm_req.active && !no_fuse && !f && p.alpha == 1.f && !p.bias && !p.gamma && p.act == LLMSEG_ACT_NONE && p.M >= 64 && p.M < wg_max_rows &&
-                           p.N >= 2048 && p.N <= 8192 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.res || (p.ldr & 7) == 0) && (g_norm_req.ldn & 7) == 0 &&
-                           ((((uintptr_t)p.C) | ((uintptr_t)p.res) | ((uintptr_t)g_norm_req.w) | ((uintptr_t)g_norm_req.out)) & 15) == 0;
-    const bool fuse_nb = g_nb_req.active && !f && p.alpha == 1.f && !p.bias && !p.gamma && !p.res && p.act == LLMSEG_ACT_NONE && p.M >= 64 && p.N >= 2048 && p.N <= 8192 &&
-                         (p.N & 7) == 0;       // == where llmseg_norm_bwd_add runs its workgroup-per-row kernel (same arithmetic, same bits)
-    const bool fuse_dl = g_dl_req.active && !f && !p.bias && !p.gamma && !p.res && p.act == LLMSEG_ACT_NONE && p.N <= 8192 && (p.N & 127) == 0 && (p.ldc & 7) == 0;
+    const bool fuse_norm = tail && tail->kind == TAIL_NORM && !f && p.alpha == 1.f && !p.bias && !p.gamma && p.act == LLMSEG_ACT_NONE && p.M >= 64 && p.M < wg_max_rows &&
+                           p.N >= 2048 && p.N <= 8192 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.res || (p.ldr & 7) == 0) && (r->ldn & 7) == 0 &&
+                           ((((uintptr_t)p.C) | ((uintptr_t)p.res) | ((uintptr_t)r->norm_w) | ((uintptr_t)r->norm_out)) & 15) == 0;
+    const bool fuse_nb = tail && tail->kind == TAIL_NB && !f && p.alpha == 1.f && !p.bias && !p.gamma && !p.res && p.act == LLMSEG_ACT_NONE && p.M >= 64 && p.N >= 2048 &&
+                         p.N <= 8192 && (p.N & 7) == 0;       // == where llmseg_norm_bwd_add runs its workgroup-per-row kernel (same arithmetic, same bits)
+    const bool fuse_dl = tail && tail->kind == TAIL_DL && !f && !p.bias && !p.gamma && !p.res && p.act == LLMSEG_ACT_NONE && p.N <= 8192 && (p.N & 127) == 0 && (p.ldc & 7) == 0;
     if (fuse_dl) {
-      const llmseg_gemm_args* q = g_dl_req.a;
-      const int S2 = split + (p.A2 ? 1 : 0);
-      const int cpt = ((p.N >> 3) + 255) / 256;
-#define LL_RDL(C) LL_LAUNCH_KERNEL(splitk_reduce_delta_kernel<C>, dim3((unsigned)p.M), dim3(256), 0, s, p, (const float*)a->workspace, S2, (const bf16_t*)q->dl_o, \
-                                   (long)q->dl_ldo, q->dl_out, (int)q->dl_heads, (int)q->dl_T)
+#define LL_RDL(C) LL_LAUNCH_KERNEL(splitk_reduce_delta_kernel<C>, dim3((unsigned)p.M), dim3(256), 0, s, p, slabs, S2, (const bf16_t*)r->dl_o, (long)r->dl_ldo, r->dl_out, \
+                                   (int)r->dl_heads, (int)r->dl_T)
       if (cpt <= 1) LL_RDL(1); else if (cpt <= 2) LL_RDL(2); else LL_RDL(4);
 #undef LL_RDL
-      g_dl_req.done = true;
     } else if (fuse_nb) {
-      const llmseg_gemm_args* q = g_nb_req.a;
-      const int rc = llmseg_reduce_lora_normbwd((const float*)a->workspace, split + (p.A2 ? 1 : 0), p.M, p.N, q->nb_x, q->nb_w, g_nb_req.out, q->nb_eps, q->nb_rms, q->nb_dres,
-                                                (void*)q->nb_lora_t, q->nb_lora_ldt, q->nb_lora_w0, q->nb_lora_w1, q->nb_lora_alpha, (const llmseg_dropout*)q->nb_lora_drop,
-                                                q->nb_lora_part, q->nb_lora_S, q->nb_lora_scale, q->nb_lora_zero, stream);
+      const int rc = llmseg_reduce_lora_normbwd(slabs, S2, p.M, p.N, r->nb_x, r->nb_w, r->C, r->nb_eps, r->nb_rms, r->nb_dres, (void*)r->nb_lora_t, r->nb_lora_ldt, r->nb_lora_w0,
+                                                r->nb_lora_w1, r->nb_lora_alpha, (const llmseg_dropout*)r->nb_lora_drop, r->nb_lora_part, r->nb_lora_S, r->nb_lora_scale,
+                                                r->nb_lora_zero, stream);
       if (rc != LLMSEG_OK) return rc;
-      g_nb_req.done = true;
     } else if (fuse_norm) {
-      const int S2 = split + (p.A2 ? 1 : 0);
-      const int cpt = ((p.N >> 3) + 255) / 256;
-      if (cpt <= 1) LL_LAUNCH_KERNEL(splitk_reduce_rmsnorm_kernel<1>, dim3((unsigned)p.M), dim3(256), 0, s, p, (const float*)a->workspace, S2, g_norm_req.w, g_norm_req.eps, g_norm_req.out, g_norm_req.ldn);
-      else if (cpt <= 2) LL_LAUNCH_KERNEL(splitk_reduce_rmsnorm_kernel<2>, dim3((unsigned)p.M), dim3(256), 0, s, p, (const float*)a->workspace, S2, g_norm_req.w, g_norm_req.eps, g_norm_req.out, g_norm_req.ldn);
-      else LL_LAUNCH_KERNEL(splitk_reduce_rmsnorm_kernel<4>, dim3((unsigned)p.M), dim3(256), 0, s, p, (const float*)a->workspace, S2, g_norm_req.w, g_norm_req.eps, g_norm_req.out, g_norm_req.ldn);
-      g_norm_req.done = true;
-    } else
-    LL_LAUNCH_KERNEL(splitk_reduce_kernel, dim3(rg), dim3(256), 0, s, p, (const float*)a->workspace, split + (p.A2 ? 1 : 0), f ? 1 : 0);
+#define LL_RNORM(C) LL_LAUNCH_KERNEL(splitk_reduce_rmsnorm_kernel<C>, dim3((unsigned)p.M), dim3(256), 0, s, p, slabs, S2, (const bf16_t*)r->norm_w, r->norm_eps, \
+                                     (bf16_t*)r->norm_out, (long)r->ldn)
+      if (cpt <= 1) LL_RNORM(1); else if (cpt <= 2) LL_RNORM(2); else LL_RNORM(4);
+#undef LL_RNORM
+    } else {
+      const long total4 = (long)p.M * (p.N >> 2);
+      const unsigned rg = (unsigned)std::min<long>((total4 + 255) / 256, 4096);
+      LL_LAUNCH_KERNEL(splitk_reduce_kernel, dim3(rg), dim3(256), 0, s, p, slabs, S2, f ? 1 : 0);
+    }
+    if (fuse_dl || fuse_nb || fuse_norm) tail->done = true;
+  } else if (pp) {
+    // one K-slice of a ping-pong tile (K_T160 never gets here: every plan of it has slices).  Fused Llama-layer epilogues (llmseg_gemm_args.fx) on shapes whose
+    // tiles hold whole pairs; gemm_fx runs the pointwise launch otherwise.  The 128-row tile serves the layer at 2 images per micro-step, the 256-row tile the fused
+    // accumulation window and 24-image micro-batches.
+    dim3 grid(p.tiles_m * p.tiles_n, (unsigned)batch);
+    const bool fx_ok = tail && tail->kind == TAIL_FX && !f && batch == 1 &&
+                       (a->fx == LLMSEG_FX_ROPE ? (p.N % 256) == 0 && p.A2 != nullptr
+                        : a->fx == LLMSEG_FX_SWIGLU ? (p.fx_I % 128) == 0 : (p.N % 64) == 0);
+    if (fx_ok) {
+      GemmP q = p;
+      q.fx = a->fx;
+      if (a->fx == LLMSEG_FX_SWIGLU_BWD) q.C = (bf16_t*)a->C - a->N;      // gemm_fx pointed C at the up half for the two-launch route: back to the row start
+      if (a->fx == LLMSEG_FX_ROPE) launch_pp<false, true, FX_ROPE>(kernel, q, grid, s);
+      else if (a->fx == LLMSEG_FX_SWIGLU) launch_pp<false, false, FX_SWIGLU>(kernel, q, grid, s);
+      else launch_pp<false, false, FX_SWIGLU_BWD>(kernel, q, grid, s);
+      tail->done = true;
+    } else if (p.A2) launch_pp<false, true>(kernel, p, grid, s);      // bf16 out only (checked above)
+    else if (f) launch_pp<true, false>(kernel, p, grid, s);
+    else launch_pp<false, false>(kernel, p, grid, s);
   } else {
     dim3 grid(p.tiles_m * p.tiles_n, (unsigned)batch);
-    switch (variant) {
-      case 2: f ? launch_glds<true, 2, 1>(p, grid, s) : launch_glds<false, 2, 1>(p, grid, s); break;
-      case 3:
-        if (f) LL_LAUNCH_KERNEL((gemm_bf16_tn_g4_kernel<true>), grid, dim3(NT), 0, s, p);
-        else LL_LAUNCH_KERNEL((gemm_bf16_tn_g4_kernel<false>), grid, dim3(NT), 0, s, p);
-        break;
-      case 8: {
-        // fused Llama-layer epilogues at large M (the fused accumulation window, 24-image micro-batches): the 256 x 256 tile's FX forms
-        const bool fx_ok8 = a->fx && !g_fx_off && !f && batch == 1 &&
-                            (a->fx == LLMSEG_FX_ROPE ? (p.N % 256) == 0 && p.A2 != nullptr
-                             : a->fx == LLMSEG_FX_SWIGLU ? (p.fx_I % 128) == 0 : (p.N % 64) == 0);
-        if (fx_ok8) {
-          GemmP q = p;
-          q.fx = a->fx;
-          if (a->fx == LLMSEG_FX_SWIGLU_BWD) q.C = (bf16_t*)a->C - a->N;
-          if (a->fx == LLMSEG_FX_ROPE) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<false, true, 4, FX_ROPE>), grid, dim3(NTB), 0, s, q);
-          else if (a->fx == LLMSEG_FX_SWIGLU) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<false, false, 4, FX_SWIGLU>), grid, dim3(NTB), 0, s, q);
-          else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<false, false, 4, FX_SWIGLU_BWD>), grid, dim3(NTB), 0, s, q);
-          g_fx_done = true;
-          break;
-        }
-        if (p.A2) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<false, true, 4>), grid, dim3(NTB), 0, s, p);      // bf16 out only (checked above)
-        else if (f) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<true, false, 4>), grid, dim3(NTB), 0, s, p);
-        else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<false, false, 4>), grid, dim3(NTB), 0, s, p);
-        break;
-      }
-      case 9:
-        if (g_gemm_pp2 == 2 && !p.A2) {                     // loader-wave form (experiment; the LoRA extension tile keeps the two-phase kernel)
-          if (f) LL_LAUNCH_KERNEL((gemm_bf16_tn_lw_kernel<true>), grid, dim3(NTL), 0, s, p);
-          else LL_LAUNCH_KERNEL((gemm_bf16_tn_lw_kernel<false>), grid, dim3(NTL), 0, s, p);
-          break;
-        }
-        if (g_gemm_pp2) {
-          // fused Llama-layer epilogues (llmseg_gemm_args.fx): this kernel, one K-slice; shapes whose tiles hold whole pairs (gemm_fx runs the pointwise launch otherwise)
-          const bool fx_ok = a->fx && !g_fx_off && !f && batch == 1 &&
-                             (a->fx == LLMSEG_FX_ROPE ? (p.N % 256) == 0 && p.A2 != nullptr
-                              : a->fx == LLMSEG_FX_SWIGLU ? (p.fx_I % 128) == 0 : (p.N % 64) == 0);
-          if (fx_ok) {
-            GemmP q = p;
-            q.fx = a->fx;
-            if (a->fx == LLMSEG_FX_SWIGLU_BWD) q.C = (bf16_t*)a->C - a->N;      // gemm_fx pointed C at the up half for the two-launch route: back to the row start
-            if (a->fx == LLMSEG_FX_ROPE) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<false, true, FX_ROPE>), grid, dim3(NTB), 0, s, q);
-            else if (a->fx == LLMSEG_FX_SWIGLU) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<false, false, FX_SWIGLU>), grid, dim3(NTB), 0, s, q);
-            else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<false, false, FX_SWIGLU_BWD>), grid, dim3(NTB), 0, s, q);
-            g_fx_done = true;
-            break;
-          }
-          if (p.A2) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<false, true>), grid, dim3(NTB), 0, s, p);
-          else if (f) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<true, false>), grid, dim3(NTB), 0, s, p);
-          else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<false, false>), grid, dim3(NTB), 0, s, p);
-          break;
-        }
-        if (p.A2) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<false, true, 2>), grid, dim3(NTB), 0, s, p);
-        else if (f) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<true, false, 2>), grid, dim3(NTB), 0, s, p);
-        else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<false, false, 2>), grid, dim3(NTB), 0, s, p);
-        break;
-      default: {
-        const int key = (f ? 4 : 0) | (ta ? 2 : 0) | (tw ? 1 : 0);
-        switch (key) {
-          case 0: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, false, false>), grid, dim3(NT), 0, s, p); break;
-          case 1: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, false, true>), grid, dim3(NT), 0, s, p); break;
-          case 2: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, true, false>), grid, dim3(NT), 0, s, p); break;
-          case 3: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, true, true>), grid, dim3(NT), 0, s, p); break;
-          case 4: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, false>), grid, dim3(NT), 0, s, p); break;
-          case 5: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, true>), grid, dim3(NT), 0, s, p); break;
-          case 6: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, false>), grid, dim3(NT), 0, s, p); break;
-          default: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, true>), grid, dim3(NT), 0, s, p); break;
-        }
+    if (kernel == K_GLDS) {
+      if (f) LL_LAUNCH_KERNEL((gemm_bf16_tn_glds_kernel<true>), grid, dim3(NT), 0, s, p);
+      else LL_LAUNCH_KERNEL((gemm_bf16_tn_glds_kernel<false>), grid, dim3(NT), 0, s, p);
+    } else {
+      const int key = (f ? 4 : 0) | (ta ? 2 : 0) | (tw ? 1 : 0);
+      switch (key) {
+        case 0: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, false, false>), grid, dim3(NT), 0, s, p); break;
+        case 1: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, false, true>), grid, dim3(NT), 0, s, p); break;
+        case 2: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, true, false>), grid, dim3(NT), 0, s, p); break;
+        case 3: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, true, true>), grid, dim3(NT), 0, s, p); break;
+        case 4: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, false>), grid, dim3(NT), 0, s, p); break;
+        case 5: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, true>), grid, dim3(NT), 0, s, p); break;
+        case 6: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, false>), grid, dim3(NT), 0, s, p); break;
+        default: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, true>), grid, dim3(NT), 0, s, p); break;
       }
     }
   }

@@ -1,6 +1,6 @@
 """GPU box: is a failing full-depth gradient seed a kernel problem or one unlucky draw of bf16 rounding noise?  For seed S:
   (A) `python tools/probes/fd_seed_diag.py S full`   HIP micro-step + fp32 oracle + bf16-CPU oracle -> gpurun_out/fd_seed{S}_A.pt (head tensors only)
-  (B) `LLMSEG_GEMM_PP2=0 LLMSEG_GEMM_NO_NORM_FUSE=1 LLMSEG_ATTN_BWD_SPLIT=1 LLMSEG_GEMM_G4=0 python tools/probes/fd_seed_diag.py S hip B`
+  (B) `LLMSEG_GEMM_NO_NORM_FUSE=1 LLMSEG_ATTN_BWD_SPLIT=1 python tools/probes/fd_seed_diag.py S hip B`
       the SAME arithmetic through other kernels / launch sets (another summation order only) -> gpurun_out/fd_seed{S}_B.pt
 `python tools/probes/fd_seed_diag.py S report` (CPU) prints per tensor: err(HIP A), err(HIP B), err(bf16-CPU), |HIP A - HIP B|."""
 import sys

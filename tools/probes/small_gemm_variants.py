@@ -9,12 +9,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from llmseg_amd import _lib, ops  # noqa: E402
 
 SHAPES = [(514, 3072, 1024), (514, 1024, 1024), (514, 4096, 1024), (514, 1024, 4096), (512, 2048, 256), (512, 256, 2048), (512, 768, 256), (638, 4096, 4096)]
-VARS = ["5", "2", "0", "9:0:2", "9:2:2", "9:4:2", "9:8:2", "8"]
+VARS = ["5", "2", "0", "9:0", "9:2", "9:4", "9:8", "8"]
 
 
 def var(spec):
     f = spec.split(":")
-    return int(f[0]) | (int(f[1]) << 8 if len(f) > 1 and f[1] else 0) | ((int(f[2]) + 1) << 13 if len(f) > 2 and f[2] else 0)
+    return int(f[0]) | (int(f[1]) << 8 if len(f) > 1 and f[1] else 0)
 
 
 lib = _lib.load()
