@@ -470,13 +470,16 @@ int llmseg_lora_down(const void* x0, const void* x1, int64_t ldx, const void* w0
  * split along K over several workgroups per 16-row tile so that the whole chip fetches the operand, a second launch adds the slices */
 int llmseg_lora_down_ws(const void* x0, const void* x1, int64_t ldx, const void* w0, const void* w1, void* y, int64_t ldy, int64_t M, int64_t K,
                         int32_t w_kr, float alpha, int32_t zero_cols, const llmseg_dropout* drop, void* scratch, int64_t scratch_bytes, void* stream);
-/* workspace: up to 32 row slices x (1 or 2 branches) x 8 N floats of partials (NULL: one slice) */
+/* workspace: row slices x nz (1 or 2 products) x 8 N floats of partials (NULL, or room for fewer than two slices: one slice, no fold launch).
+ * The dispatch takes max(1, 256 / (ceil(N / 64) * nz), min(32, M / 512)) slices -- 256 for N = 8 with one product -- cut to what the
+ * workspace holds; slices * nz * 8 N * 4 bytes lets every slice be taken (at most 256 * 8 * 64 * 4 = 512 KiB below M = 1024, 32 slices above). */
 int llmseg_lora_outer(const void* a0, const void* a1, int64_t lda, const void* b0, const void* b1, int64_t ldb, float* out0, float* out1, int64_t M,
                       int64_t N, int32_t out_rn, float alpha, const llmseg_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream);
 /* The four weight gradients of a LoRA'd q|k|v projection in ONE launch (+ one fold): with d = dqkv (dq, dv: column blocks at row pitch ldd),
  * xa = [drop_q(x) Aq^T | drop_v(x) Av^T] [M][>= 16] (the forward's extension operand), t = [s dq Bq | s dv Bv] [M][>= 16]:
  *   gbq [H][8] += s dq^T xa[:, 0:8],  gbv [H][8] += s dv^T xa[:, 8:16],  gaq [8][H] += t[:, 0:8]^T drop_q(x),  gav [8][H] += t[:, 8:16]^T drop_v(x)
- * (dropout streams drop->stream / + 1, as llmseg_lora_down uses them).  workspace: up to 32 row slices x 4 x 8 H floats. */
+ * (dropout streams drop->stream / + 1, as llmseg_lora_down uses them).  workspace: row slices x 4 x 8 H floats,
+ * slices = max(1, 256 / (4 ceil(H / 64)), min(32, M / 512)) as for llmseg_lora_outer with nz = 4 (one slice at M = 638, H = 4096; 14 at M = 7656). */
 int llmseg_lora_wgrads(const void* dq, const void* dv, int64_t ldd, const void* x, int64_t ldx, const void* xa, int64_t ldxa, const void* t, int64_t ldt,
                        float* gbq, float* gbv, float* gaq, float* gav, int64_t M, int64_t H, float s, const llmseg_dropout* drop, void* workspace,
                        int64_t workspace_bytes, void* stream);

@@ -54,6 +54,19 @@ def _reduce_ws(dev):
     return C.c_void_p(ws.data_ptr()), ws.numel()
 
 
+_DEFAULT_WS = object()
+
+
+def _ws_arg(workspace, dev):
+    """(pointer, bytes) of a reduction's `workspace=` keyword: the default is `_reduce_ws`, None passes NULL / 0, a uint8 tensor passes that buffer and its size."""
+    if workspace is _DEFAULT_WS:
+        return _reduce_ws(dev)
+    if workspace is None:
+        return None, 0
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    return C.c_void_p(workspace.data_ptr()), workspace.numel()
+
+
 def gemm(a, w, bias=None, act=ACT_NONE, residual=None, gamma=None, out=None, alpha=1.0, out_f32=False, trans_a=False, trans_w=False,
          a2=None, w2=None, accumulate=False, a_norm_w=None, a_norm_eps=1e-6, a_swiglu=False, norm_w=None, norm_eps=1e-6, norm_out=None,
          rope=None, swiglu_out=None, swiglu_bwd_of=None, normbwd=None, nb_lora=None, delta_of=None):
@@ -555,21 +568,21 @@ def union_resize_iou(segs_hwk_u8, select_u8, gt_u8, out_size=1024, ignore_index=
 
 
 # ---- backward / optimizer -------------------------------------------------------------------------------------------
-def colsum(x, out=None):
+def colsum(x, out=None, workspace=_DEFAULT_WS):
     M, N = x.shape
     if out is None:
         out = torch.zeros((N,), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().llmseg_colsum(_ptr(x), _ptr(out), M, N, x.stride(0), *_reduce_ws(x.device), _stream()), "colsum")
+    _lib.check(_lib.load().llmseg_colsum(_ptr(x), _ptr(out), M, N, x.stride(0), *_ws_arg(workspace, x.device), _stream()), "colsum")
     return out
 
 
-def norm_bwd(dy, x, w, eps, rms, dw=None, db=None, dres=None):
+def norm_bwd(dy, x, w, eps, rms, dw=None, db=None, dres=None, workspace=_DEFAULT_WS):
     """dres: gradient reaching x through a residual connection, added to dx in the same pass."""
     rows, cols = x.shape
     assert dy.is_contiguous() and x.is_contiguous() and (dres is None or (dres.is_contiguous() and dres.shape == x.shape))
     dx = torch.empty_like(x)
     _lib.check(_lib.load().llmseg_norm_bwd_add(_ptr(dy), _ptr(x), _ptr(w), _ptr(dres), _ptr(dx), _ptr(dw), _ptr(db), rows, cols, eps, 1 if rms else 0,
-                                               *_reduce_ws(x.device), _stream()), "norm_bwd")
+                                               *_ws_arg(workspace, x.device), _stream()), "norm_bwd")
     return dx
 
 
@@ -600,9 +613,18 @@ def attn_ds(P, dP, T, ld, scale):
     return dS
 
 
-def ce_bwd(logits, labels, coef):
+def ce_bwd(logits, labels, coef, out=None):
+    """logits bf16 [N, T, V], possibly the leading V columns of rows ld wide.  -> dlogits with the same strides (`out`, or a fresh buffer of the same row
+    pitch: `empty_like` of such a view would be dense while the kernel writes rows at pitch ld).  Columns V .. ld of its rows are not written."""
     N, T, V = logits.shape
-    dl = torch.empty_like(logits)
+    ld = logits.stride(1)
+    if out is not None:
+        dl = out
+        assert dl.shape == logits.shape and dl.stride(1) == ld and dl.stride(2) == 1 and dl.dtype == logits.dtype
+    elif ld == V:
+        dl = torch.empty_like(logits)
+    else:
+        dl = torch.empty((N, T, ld), device=logits.device, dtype=logits.dtype)[..., :V]
     _lib.check(_lib.load().llmseg_ce_bwd(_ptr(logits), _ptr(labels), _ptr(coef), _ptr(dl), N, T, V, logits.stride(1), _stream()), "ce_bwd")
     return dl
 
@@ -623,19 +645,20 @@ def _drop(drop):
     return C.byref(_lib.Dropout(rng_state=rng.data_ptr(), stream=int(stream), drop_thr=int(round(p * 65536)), seg_rows=seg, reserved0=0))
 
 
-def lora_down(x, w, w_kr=False, alpha=1.0, out=None, zero_cols=0, drop=None, x2=None, w2=None, pack=None, parts=False):
+def lora_down(x, w, w_kr=False, alpha=1.0, out=None, zero_cols=0, drop=None, x2=None, w2=None, pack=None, parts=False, scratch=True):
     """y [M, 8] = alpha * drop(x) [M, K] @ W^T; W stored [8, K] (or [K, 8] when w_kr).  x may be a column view (row stride = ld).
     With (x2, w2) the second branch lands in columns 8..15 of the same rows (its dropout stream is drop's + 1; x2 may be x).  `out`
     may be the leading columns of a wider row; `zero_cols` further columns of every row are zero-filled.
     pack = (aq, bq, av, bv, s, w2b, w2a, bt): `lora_pack` of the same layer in the same call (`llmseg_lora_down_pack`: it rides in the K-slice finish launch).
     parts=True (`llmseg_lora_down_parts`): -> (y, partials | None, S, scale): where the product runs as K slices it is left UNFINISHED (y not written; hand
-    (partials, S, scale, zero_cols) to `gemm(..., nb_lora=)`, whose tail finishes it and writes y); S = 0: y is complete."""
+    (partials, S, scale, zero_cols) to `gemm(..., nb_lora=)`, whose tail finishes it and writes y); S = 0: y is complete.
+    scratch=False: no K-slice scratch is handed over (the product runs unsliced)."""
     M, K = x.shape
     nb = 1 if w2 is None else 2
     y = torch.empty((M, 8 * nb), device=x.device, dtype=BF16) if out is None else out
     assert y.shape[0] == M and y.stride(1) == 1 and (x2 is None or (x2.shape == x.shape and x2.stride(0) == x.stride(0)))
-    scratch = None
-    if not w_kr and (M + 15) // 16 < 256 and K % 256 == 0:       # short activations: K-sliced over several workgroups per row tile (fp32 partials)
+    want_scratch, scratch = scratch, None
+    if want_scratch and not w_kr and (M + 15) // 16 < 256 and K % 256 == 0:       # short activations: K-sliced over several workgroups per row tile (fp32 partials)
         scratch = torch.empty((32 * 2 * M * 16,), device=x.device, dtype=torch.float32)
     args = (_ptr(x), _ptr(x2 if w2 is not None and x2 is not None else (x if w2 is not None else None)), x.stride(0),
             _ptr(w), _ptr(w2), _ptr(y), y.stride(0), M, K, 1 if w_kr else 0, alpha, zero_cols, _drop(drop),
@@ -656,7 +679,7 @@ def lora_down(x, w, w_kr=False, alpha=1.0, out=None, zero_cols=0, drop=None, x2=
     return y
 
 
-def lora_outer(a, b, out_rn=False, alpha=1.0, out=None, drop=None, a2=None, b2=None, out2=None):
+def lora_outer(a, b, out_rn=False, alpha=1.0, out=None, drop=None, a2=None, b2=None, out2=None, workspace=_DEFAULT_WS):
     """out [N, 8] (or [8, N] when out_rn) += alpha * drop(a)[M, N]^T @ b[M, 8], fp32 (a fresh zero buffer unless `out` is given).
     With (a2, b2) a second, independent product of the same shapes runs in the same launch (dropout stream + 1) -> (out, out2)."""
     M, N = a.shape
@@ -670,12 +693,12 @@ def lora_outer(a, b, out_rn=False, alpha=1.0, out=None, drop=None, a2=None, b2=N
             out2 = torch.zeros(shape, device=a.device, dtype=torch.float32)
         assert a2.shape == a.shape and a2.stride(0) == a.stride(0) and b2.stride(0) == b.stride(0) and out2.is_contiguous() and out2.numel() == 8 * N
     _lib.check(_lib.load().llmseg_lora_outer(_ptr(a), _ptr(a2 if b2 is not None else None), a.stride(0), _ptr(b), _ptr(b2), b.stride(0), _ptr(out),
-                                             _ptr(out2 if b2 is not None else None), M, N, 1 if out_rn else 0, alpha, _drop(drop), *_reduce_ws(a.device),
+                                             _ptr(out2 if b2 is not None else None), M, N, 1 if out_rn else 0, alpha, _drop(drop), *_ws_arg(workspace, a.device),
                                              _stream()), "lora_outer")
     return out if b2 is None else (out, out2)
 
 
-def lora_wgrads(d, H, x, a2, t2, gbq, gbv, gaq, gav, s, drop=None):
+def lora_wgrads(d, H, x, a2, t2, gbq, gbv, gaq, gav, s, drop=None, workspace=_DEFAULT_WS):
     """The four LoRA weight gradients of a q|k|v projection in one launch: d = dqkv [M, 3H] (q block = columns 0..H, v block = 2H..3H),
     x [M, H] the projection's input, a2 [M, >= 16] = [drop_q(x) Aq^T | drop_v(x) Av^T], t2 [M, >= 16] = [s dq Bq | s dv Bv];
     gbq / gbv fp32 [H, 8] and gaq / gav fp32 [8, H] are accumulated into (arena views)."""
@@ -685,7 +708,7 @@ def lora_wgrads(d, H, x, a2, t2, gbq, gbv, gaq, gav, s, drop=None):
     assert d.stride(1) == 1 and x.stride(1) == 1 and a2.stride(1) == 1 and t2.stride(1) == 1 and x.shape == (M, H)
     dq, dv = d[:, :H], d[:, 2 * H:]
     _lib.check(_lib.load().llmseg_lora_wgrads(_ptr(dq), _ptr(dv), d.stride(0), _ptr(x), x.stride(0), _ptr(a2), a2.stride(0), _ptr(t2), t2.stride(0),
-                                              _ptr(gbq), _ptr(gbv), _ptr(gaq), _ptr(gav), M, H, s, _drop(drop), *_reduce_ws(d.device), _stream()), "lora_wgrads")
+                                              _ptr(gbq), _ptr(gbv), _ptr(gaq), _ptr(gav), M, H, s, _drop(drop), *_ws_arg(workspace, d.device), _stream()), "lora_wgrads")
 
 
 def lora_apply_(y, xa, w, w_rn=False, alpha=1.0, drop=None, w2=None):
@@ -706,8 +729,8 @@ def lora_pack(aq, bq, av, bv, s, w2b=None, w2a=None, bt=None):
     _lib.check(_lib.load().llmseg_lora_pack(_ptr(aq), _ptr(bq), _ptr(av), _ptr(bv), _ptr(w2b), _ptr(w2a), _ptr(bt), H, s, _stream()), "lora_pack")
 
 
-def sumsq(x, out):
-    _lib.check(_lib.load().llmseg_sumsq(_ptr(x), x.numel(), 1 if x.dtype == torch.float32 else 0, _ptr(out), *_reduce_ws(x.device), _stream()), "sumsq")
+def sumsq(x, out, workspace=_DEFAULT_WS):
+    _lib.check(_lib.load().llmseg_sumsq(_ptr(x), x.numel(), 1 if x.dtype == torch.float32 else 0, _ptr(out), *_ws_arg(workspace, x.device), _stream()), "sumsq")
     return out
 
 
