@@ -21,6 +21,7 @@ extern "C" {
 #define LLMSEG_OK 0
 #define LLMSEG_EINVAL (-1)
 #define LLMSEG_ELAUNCH (-2)
+#define LLMSEG_NOT_TAKEN 1 /* llmseg_linear_bwd: the shape is not covered, nothing was launched or written; the caller runs the separate kernels */
 
 /* epilogue activation */
 enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT_QUICKGELU = 3, LLMSEG_ACT_SILU = 4,
@@ -31,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 9
+#define LLMSEG_ABI_VERSION 10
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -426,6 +427,15 @@ int llmseg_norm_bwd_add(const void* dy, const void* x, const void* w, const void
 int llmseg_swiglu_bwd(const void* gu, const void* dout, void* dgu, int64_t rows, int64_t I, void* stream);
 /* out = dy * f'(y) computed from the OUTPUT y of a fused GEMM epilogue (act = RELU or SIGMOID) */
 int llmseg_act_bwd(const void* dy, const void* y, void* out, int64_t n, int act, void* stream);
+/* Backward of a SMALL trainable Linear y = act(x W^T + b) in ONE launch (ABI 10): dy, y [M][N], x [M][K], w [N][K], all bf16 and dense (row pitch = width).
+ *   dpre = dy * act'(y) with llmseg_act_bwd's arithmetic, rounded to bf16 (act = NONE: dpre = dy and y may be NULL; else RELU or SIGMOID);
+ *   dx [M][K] bf16 = dpre W;   dw [N][K] fp32 = dpre^T x;   db [N] fp32 = column sums of dpre.   Any of dx / dw / db may be NULL (skipped).
+ * accumulate = 1: dw and db are `+=` (the fp32 gradient arena), 0: they are overwritten.  A workgroup owns a 32 x 64 tile of dw (or of dx, a second range of the
+ * same grid) and walks the whole contraction (M rows, or N columns) itself: no partial sums leave the workgroup, every sum has a fixed order, no workspace.
+ * Any M, N, K >= 1 (N = 1, M % 16 != 0, K % 64 != 0 are handled in the kernel; rows whose pitch is not a multiple of 8 elements are read element-wise).
+ * Returns LLMSEG_NOT_TAKEN without launching when M > 2048 or N K > 2^22: there the walk is too long for one workgroup (wide Linears, lm_head). */
+int llmseg_linear_bwd(const void* dy, const void* y, int act, const void* x, const void* w, void* dx, float* dw, float* db, int64_t M, int64_t N, int64_t K,
+                      int accumulate, void* stream);
 /* Materialised attention probabilities for the backward pass (T <= a few hundred: Llama T=319, head K<=512):
  * P[b][q][k] = softmax_k(scale * S[b][q][k] + causal/key mask), S fp32 [BH][Tq][ld], P bf16 same shape, columns >= Tk zero.
  * key_mask uint8 [BH/heads][Tk] or NULL; causal requires Tq == Tk. */

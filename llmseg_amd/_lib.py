@@ -10,9 +10,10 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 9          # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 10         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
+NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
 
 
 class _Sized(C.Structure):
@@ -130,6 +131,7 @@ SIGNATURES = {
     "llmseg_norm_bwd_add": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, C.c_int, _p, _i64, _p],
     "llmseg_swiglu_bwd": [_p, _p, _p, _i64, _i64, _p],
     "llmseg_act_bwd": [_p, _p, _p, _i64, C.c_int, _p],
+    "llmseg_linear_bwd": [_p, _p, C.c_int, _p, _p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p],
     "llmseg_softmax_rows": [_p, _p, _i64, _i32, _i32, _i32, _f32, _i32, _p, _i32, _p],
     "llmseg_attn_ds": [_p, _p, _p, _i64, _i32, _i32, _f32, _p],
     "llmseg_ce_bwd": [_p, _p, _p, _p, _i32, _i32, _i64, _i64, _p],

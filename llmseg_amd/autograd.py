@@ -31,6 +31,7 @@ FUSE_NORM_BWD = os.environ.get("LLMSEG_NO_FUSE_NORM_BWD") is None      # pre-nor
 FUSE_LORA_PARTS = os.environ.get("LLMSEG_NO_FUSE_LORA_PARTS") is None  # the backward's rank-8 down projection is finished inside the dX(q|k|v) product's tail
 FUSE_DELTA = os.environ.get("LLMSEG_NO_FUSE_DELTA") is None            # the attention backward's delta inside the dX(o_proj) product's reduce launch
 FUSE_MLP = os.environ.get("LLMSEG_NO_FUSE_MLP") is None                # swiglu / swiglu_bwd inside the gate|up and dX(down) GEMMs' stores (frozen MLP weights)
+FUSE_LINEAR_BWD = os.environ.get("LLMSEG_NO_FUSE_LINEAR_BWD") is None  # a small trainable Linear's act_bwd + dX + dW + db as ONE launch (`llmseg_linear_bwd`)
 
 
 class Leaves:
@@ -108,13 +109,25 @@ class LinearFn(Function):
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
         dy = dy.contiguous()
-        dpre = ops.act_bwd(dy, y, ctx.act) if ctx.act != ops.ACT_NONE else dy
         N = w.shape[0]
         M, Kin = x.shape
         dx = dw = db = None
         gw = ctx.gw
         need_w = gw is not None or ctx.needs_input_grad[1]
         big = M * N * Kin >= BIG_LINEAR or (N * Kin >= BIG_WEIGHT and M >= 16)      # the weight itself is big: also with few rows (lm_head on the label rows only)
+        dres = dy if (ctx.has_res and ctx.needs_input_grad[4]) else None
+        if FUSE_LINEAR_BWD and not Leaves.on and not (big and Kin % 8 == 0) and not (ctx.wt is not None and N % 8 == 0):
+            # small trainable Linear (the mask head, text_hidden_fcs): ONE launch forms dpre = dy * act'(y), dx, dW and db; the arena views are added to in place
+            need_b = ctx.gb is not None or (ctx.b_needs and ctx.needs_input_grad[2])
+            acc = gw is not None or ctx.gb is not None
+            new = torch.zeros if acc else torch.empty                                # a plain output beside an arena one is added to as well
+            fw = gw if gw is not None else (new((N, Kin), device=x.device, dtype=torch.float32) if need_w else None)
+            fb = ctx.gb if ctx.gb is not None else (new((N,), device=x.device, dtype=torch.float32) if need_b else None)
+            if ctx.needs_input_grad[0] or fw is not None or fb is not None:
+                r = ops.linear_bwd(dy, y, ctx.act, x.contiguous(), w.contiguous(), want_dx=ctx.needs_input_grad[0], dw=fw, db=fb, accumulate=acc)
+                if not isinstance(r, str):
+                    return (r, fw.to(BF16) if (gw is None and need_w) else None, fb.to(BF16) if (ctx.gb is None and need_b) else None, None, dres, None)
+        dpre = ops.act_bwd(dy, y, ctx.act) if ctx.act != ops.ACT_NONE else dy
         if big and Kin % 8 == 0 and (need_w or ctx.wt is None or N % 8 != 0):
             # wide trainable Linear (lm_head, [32004, 4096]): pad the contraction dims to multiples of 64 and transpose the
             # operands once, so that both gradient GEMMs run on the K-contiguous LDS-DMA kernels instead of the
@@ -155,7 +168,6 @@ class LinearFn(Function):
             Leaves.run(lambda: ops.colsum(dpre, out=ctx.gb), dpre)
         elif ctx.b_needs and ctx.needs_input_grad[2]:
             db = ops.colsum(dpre).to(BF16)
-        dres = dy if (ctx.has_res and ctx.needs_input_grad[4]) else None
         return dx, dw, db, None, dres, None
 
 

@@ -1311,3 +1311,204 @@ extern "C" int llmseg_transpose_pad(const void* in, void* out, int64_t rows, int
   LL_LAUNCH_CHECK("transpose_pad");
   return LLMSEG_OK;
 }
+
+// ---- small trainable Linear y = act(x W^T + b): dX, dW += and db += in ONE launch (llmseg_linear_bwd) ------------------------------------------
+// The head's Linears (a few hundred rows, weights of 256 x 256 .. 256 x 2048) used to cost five to seven launches each: act_bwd, the dX product, the dW product as
+// K-slices + their reduce, colsum as row slices + their fold.  Here a workgroup owns a 32 x 64 tile of an OUTPUT and walks the whole contraction itself:
+//   range W of the grid:  dW[n][k] = sum_m dpre[m][n] x[m][k]    (tile rows = n, contraction = m; the k-tile 0 workgroups also form db[n] = sum_m dpre[m][n])
+//   range X of the grid:  dX[m][k] = sum_n dpre[m][n] w[n][k]    (tile rows = m, contraction = n)
+// Both are C[i][k] = sum_c A[i][c] B[c][k] with B stored [c][k] (k contiguous) and A stored [c][i] (range W) or [i][c] (range X).  The contraction runs in chunks of
+// 256: the chunk of A and of B goes to LDS with c contiguous (AT[i][c], BT[k][c]: a transposition for B and for range W's A, two c per 32-bit LDS store), wave w takes
+// c in [64 w, 64 w + 64) of every chunk with v_mfma_f32_16x16x32_bf16 (2 x 4 blocks of 16 x 16), and the four waves' accumulators are folded through LDS in wave order.
+// dpre = dy * act'(y) is formed while the chunk is staged, with act_bwd_kernel's expression and its bf16 rounding.  Everything outside the matrices reads as zero.
+namespace {
+constexpr int LB_TI = 32, LB_TK = 64, LB_CC = 256, LB_LD = LB_CC + 8;        // tile rows, tile columns, contraction chunk, LDS row pitch (elements)
+
+struct LinBwd {
+  const bf16_t *dy, *y, *x, *w;
+  bf16_t* dx;
+  float *dw, *db;
+  int M, N, K, act, accumulate;
+  int w_it, w_kt, x_kt;          // tiles of range W (rows, columns; columns = 1 when only db is wanted), column tiles of range X
+  int vec_n, vec_k;              // 16-byte loads are legal on the [.][N] matrices (dy, y) / on the [.][K] matrices (x, w)
+};
+
+// 8 consecutive elements of row r from column c of a dense [rows][cols] bf16 matrix; zero outside the matrix
+__device__ __forceinline__ uint4 lb_load8(const bf16_t* __restrict__ p, int r, int c, int rows, int cols, bool vec) {
+  if (r >= rows || c >= cols) return make_uint4(0, 0, 0, 0);
+  const bf16_t* q = p + (long)r * cols + c;
+  if (vec) return *reinterpret_cast<const uint4*>(q);                        // cols % 8 == 0 and c % 8 == 0: the 8 elements are inside the row
+  uint32_t h[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) h[j] = c + j < cols ? (uint32_t)q[j] : 0u;
+  return make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+}
+
+// act_bwd_kernel on 8 elements
+__device__ __forceinline__ uint4 lb_act8(const uint4& g, const uint4& yv, int act) {
+  if (act == LLMSEG_ACT_NONE) return g;
+  float gf[8], yf[8];
+  uint32_t o[8];
+  unpack8(g, gf); unpack8(yv, yf);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = f2bf(act == LLMSEG_ACT_RELU ? (yf[e] > 0.f ? gf[e] : 0.f) : gf[e] * yf[e] * (1.f - yf[e]));
+  return make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
+}
+
+__device__ __forceinline__ uint32_t lb_elem(const uint4& v, int j) {         // element j (0..7) of a packed row piece
+  const uint32_t wd = (j >> 1) == 0 ? v.x : (j >> 1) == 1 ? v.y : (j >> 1) == 2 ? v.z : v.w;
+  return (j & 1) ? (wd >> 16) : (wd & 0xffffu);
+}
+
+// rows c and c + 1 (pieces lo, hi: 8 columns each) -> T[col0 + j][c .. c + 1], j = 0..7
+__device__ __forceinline__ void lb_store_t(bf16_t* T, int col0, int c, const uint4& lo, const uint4& hi) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) *reinterpret_cast<uint32_t*>(T + (col0 + j) * LB_LD + c) = lb_elem(lo, j) | (lb_elem(hi, j) << 16);
+}
+
+__global__ __launch_bounds__(256) void linear_bwd_kernel(const LinBwd p) {
+  __shared__ __attribute__((aligned(16))) bf16_t lds[(LB_TI + LB_TK) * LB_LD];          // 50688 bytes; the fold below re-uses the first 32 KiB
+  bf16_t* AT = lds;
+  bf16_t* BT = lds + LB_TI * LB_LD;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int nW = p.w_it * p.w_kt;
+  const bool roleW = (int)blockIdx.x < nW;
+  const int bi = roleW ? (int)blockIdx.x : (int)blockIdx.x - nW;
+  const int nkt = roleW ? p.w_kt : p.x_kt;
+  const int i0 = (bi / nkt) * LB_TI, k0 = (bi % nkt) * LB_TK;
+  const int C = roleW ? p.M : p.N;                                            // contraction length
+  const bf16_t* __restrict__ B = roleW ? p.x : p.w;                          // [C][K]
+  const bool vn = p.vec_n != 0, vk = p.vec_k != 0, has_act = p.act != LLMSEG_ACT_NONE;
+  const bool want_db = roleW && (bi % nkt) == 0 && p.db != nullptr;
+
+  uint4 ra[4], ry[4], rb[8];
+  // A: range W reads row pairs (c, c + 1) x 8 columns i (512 pairs, two per thread); range X reads 32 rows i x 32 pieces of 8 c (four per thread)
+  // B: row pairs (c, c + 1) x 8 columns k (1024 pairs, four per thread)
+  auto load_chunk = [&](int c0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      int r, c;
+      if (roleW) { const int pr = t + 256 * (q >> 1); r = c0 + 2 * (pr >> 2) + (q & 1); c = i0 + 8 * (pr & 3); }
+      else { const int v = t + 256 * q; r = i0 + (v >> 5); c = c0 + 8 * (v & 31); }
+      ra[q] = lb_load8(p.dy, r, c, p.M, p.N, vn);
+      if (has_act) ry[q] = lb_load8(p.y, r, c, p.M, p.N, vn);
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int pr = t + 256 * (q >> 1);
+      rb[q] = lb_load8(B, c0 + 2 * (pr >> 3) + (q & 1), k0 + 8 * (pr & 7), C, p.K, vk);
+    }
+  };
+  auto store_chunk = [&]() {
+    if (has_act) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ra[q] = lb_act8(ra[q], ry[q], p.act);
+    }
+    if (roleW) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) { const int pr = t + 256 * q; lb_store_t(AT, 8 * (pr & 3), 2 * (pr >> 2), ra[2 * q], ra[2 * q + 1]); }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { const int v = t + 256 * q; *reinterpret_cast<uint4*>(AT + (v >> 5) * LB_LD + 8 * (v & 31)) = ra[q]; }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const int pr = t + 256 * q; lb_store_t(BT, 8 * (pr & 7), 2 * (pr >> 3), rb[2 * q], rb[2 * q + 1]); }
+  };
+
+  f32x4_t acc[2][4];
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) acc[ib][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float dbacc = 0.f;
+
+  const int nch = (C + LB_CC - 1) / LB_CC;
+  load_chunk(0);
+  for (int ch = 0; ch < nch; ++ch) {
+    if (ch) __syncthreads();                                                  // the previous chunk has been read by every wave
+    store_chunk();
+    __syncthreads();
+    if (ch + 1 < nch) load_chunk((ch + 1) * LB_CC);                           // in flight during this chunk's MFMAs
+    if (want_db) {                                                            // thread = (row i = t / 8, c in [32 (t % 8), + 32) of the chunk), one term after the other
+      const bf16_t* row = AT + (t >> 3) * LB_LD + 32 * (t & 7);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        float f[8];
+        unpack8(*reinterpret_cast<const uint4*>(row + 8 * v), f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dbacc += f[e];
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int cw = wave * 64 + ks * 32;
+      if (ch * LB_CC + cw >= C) break;                                        // nothing but zeros from here on (wave-uniform)
+      const int cb = cw + 8 * (lane >> 4);
+      bf16x8_t af[2], bf[4];
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib) af[ib] = *reinterpret_cast<const bf16x8_t*>(AT + (16 * ib + (lane & 15)) * LB_LD + cb);
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) bf[kb] = *reinterpret_cast<const bf16x8_t*>(BT + (16 * kb + (lane & 15)) * LB_LD + cb);
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) acc[ib][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ib], bf[kb], acc[ib][kb], 0, 0, 0);
+    }
+  }
+
+  if (want_db) {                                                              // the row's 8 threads are 8 consecutive lanes: a fixed tree
+    dbacc += __shfl_xor(dbacc, 4, 64);
+    dbacc += __shfl_xor(dbacc, 2, 64);
+    dbacc += __shfl_xor(dbacc, 1, 64);
+    const int n = i0 + (t >> 3);
+    if ((t & 7) == 0 && n < p.N) p.db[n] = p.accumulate ? p.db[n] + dbacc : dbacc;
+  }
+  if (roleW && !p.dw) return;                                                 // db only (block-uniform)
+
+  // fold the four waves' partial tiles in wave order: fold[w][i][k], C/D layout of the MFMA: column k = lane % 16, row i = 4 (lane / 16) + e
+  float* fold = reinterpret_cast<float*>(lds);
+  __syncthreads();
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) fold[(wave * LB_TI + 16 * ib + 4 * (lane >> 4) + e) * LB_TK + 16 * kb + (lane & 15)] = acc[ib][kb][e];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int idx = t + 256 * q, i = idx >> 6, k = idx & 63;
+    float s = fold[idx];
+    s += fold[LB_TI * LB_TK + idx];
+    s += fold[2 * LB_TI * LB_TK + idx];
+    s += fold[3 * LB_TI * LB_TK + idx];
+    const int gi = i0 + i, gk = k0 + k;
+    if (gk >= p.K) continue;
+    if (roleW) {
+      if (gi < p.N) { float* o = p.dw + (long)gi * p.K + gk; *o = p.accumulate ? *o + s : s; }
+    } else if (gi < p.M) {
+      p.dx[(long)gi * p.K + gk] = f2bf(s);
+    }
+  }
+}
+}  // namespace
+
+extern "C" int llmseg_linear_bwd(const void* dy, const void* y, int act, const void* x, const void* w, void* dx, float* dw, float* db, int64_t M, int64_t N, int64_t K,
+                                 int accumulate, void* stream) {
+  LL_CHECK(dy && x && w && M > 0 && N > 0 && K > 0 && (dx || dw || db), "linear_bwd: bad arguments");
+  LL_CHECK(act == LLMSEG_ACT_NONE || ((act == LLMSEG_ACT_RELU || act == LLMSEG_ACT_SIGMOID) && y), "linear_bwd: only relu/sigmoid are differentiated, from the output y");
+  if (M > 2048 || N * K > (1L << 22)) return LLMSEG_NOT_TAKEN;               // one workgroup per output tile walks the whole contraction: small Linears only
+  LinBwd p;
+  p.dy = (const bf16_t*)dy; p.y = (const bf16_t*)y; p.x = (const bf16_t*)x; p.w = (const bf16_t*)w;
+  p.dx = (bf16_t*)dx; p.dw = dw; p.db = db;
+  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.act = act; p.accumulate = accumulate ? 1 : 0;
+  p.w_it = (dw || db) ? (int)((N + LB_TI - 1) / LB_TI) : 0;
+  p.w_kt = dw ? (int)((K + LB_TK - 1) / LB_TK) : 1;
+  p.x_kt = (int)((K + LB_TK - 1) / LB_TK);
+  p.vec_n = (N & 7) == 0 && AL16(dy) && (act == LLMSEG_ACT_NONE || AL16(y));
+  p.vec_k = (K & 7) == 0 && AL16(x) && AL16(w);
+  const long grid = (long)p.w_it * p.w_kt + (dx ? (long)((M + LB_TI - 1) / LB_TI) * p.x_kt : 0L);
+  LL_LAUNCH_KERNEL(linear_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+  LL_LAUNCH_CHECK("linear_bwd");
+  return LLMSEG_OK;
+}

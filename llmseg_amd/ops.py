@@ -600,6 +600,28 @@ def act_bwd(dy, y, act):
     return out
 
 
+def linear_bwd(dy, y, act, x, w, want_dx=True, dw=None, db=None, accumulate=False, dx=None):
+    """Backward of a small Linear y = act(x w^T + b) in ONE launch (`llmseg_linear_bwd`): dy, y [M, N], x [M, K], w [N, K] contiguous bf16.
+    -> dx bf16 [M, K] (None unless want_dx), or the string "not taken" when the library does not cover the shape (nothing launched: run the separate kernels).
+    dw [N, K] / db [N]: contiguous fp32 outputs, `+=` when accumulate (the gradient arena), overwritten otherwise; None = skipped."""
+    M, N = dy.shape
+    K = x.shape[1]
+    _req(dy); _req(x); _req(w)
+    assert dy.is_contiguous() and x.is_contiguous() and w.is_contiguous() and x.shape == (M, K) and w.shape == (N, K)
+    assert act == ACT_NONE or (_req(y).is_contiguous() and y.shape == dy.shape)
+    for g, shape in ((dw, (N, K)), (db, (N,))):
+        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and g.shape == shape and g.is_cuda)
+    if want_dx and dx is None:
+        dx = torch.empty((M, K), device=dy.device, dtype=BF16)
+    assert dx is None or (_req(dx).is_contiguous() and dx.shape == (M, K))
+    rc = _lib.load().llmseg_linear_bwd(_ptr(dy), _ptr(y) if act != ACT_NONE else None, act, _ptr(x), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db), M, N, K,
+                                       1 if accumulate else 0, _stream())
+    if rc == _lib.NOT_TAKEN:
+        return "not taken"
+    _lib.check(rc, "linear_bwd")
+    return dx
+
+
 def softmax_rows(S, BH, Tq, Tk, ld, scale, causal=False, key_mask=None, heads=1):
     P = torch.empty((BH, Tq, ld), device=S.device, dtype=BF16)
     _lib.check(_lib.load().llmseg_softmax_rows(_ptr(S), _ptr(P), BH, Tq, Tk, ld, scale, 1 if causal else 0, _ptr(key_mask), heads, _stream()),
