@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 10
+#define LLMSEG_ABI_VERSION 11
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -293,6 +293,29 @@ int llmseg_mask_small_regions(uint8_t* masks, int32_t K, int32_t H, int32_t W, i
                               int64_t workspace_bytes, void* stream);
 int llmseg_mask_boxes(const uint8_t* masks, int32_t K, int32_t H, int32_t W, int32_t* boxes, int32_t* areas, void* workspace, int64_t workspace_bytes,
                       void* stream);
+/* The raw-image front end of inference (llmseg_amd/segment.py; csrc/image.hip):
+ *   llmseg_image_resize_u8_filter: llmseg_image_resize_u8 with the resampling filter as an argument.  LLMSEG_RESAMPLE_BILINEAR is that entry
+ *     point itself (same bits, same limits); LLMSEG_RESAMPLE_BICUBIC is Pillow's 8-bit BICUBIC `Image.resize`, bit-identical (Resample.c:
+ *     a = -0.5, support = 2 * max(scale, 1), taps in double, normalised, rounded to 22-bit fixed point with -0.5 for the negative lobes,
+ *     horizontal then vertical pass with clip8 and a uint8 intermediate).  Down-scaling up to 63x per axis (255 taps).
+ *     workspace >= llmseg_image_resize_filter_workspace(...) bytes.
+ *   llmseg_clip_preprocess: `CLIPImageProcessor.preprocess` with the CLIP-L/14 settings the reference loads (utils/llm_seg_dataset.py:127):
+ *     shortest edge -> size with BICUBIC (resized long side = int(size * long / short), transformers `get_resize_output_image_size`), centre
+ *     crop size x size (origin (resized - size) / 2, rounded down), * 1/255, (x - mean[c]) / std[c].  in uint8 [h][w][3] with `in_row_stride` bytes
+ *     between rows -> out bf16 [3][size][size].  Only the crop window is resampled; both passes keep Pillow's uint8 rounding, so the result is
+ *     that of resizing the whole image, cropping and normalising.  mean / std are HOST pointers to 3 floats.
+ *     workspace >= llmseg_clip_preprocess_workspace(h, w, size) bytes.
+ *   llmseg_mask_union: out uint8 [C][H][W] = 1 where any mask k with select[c][k] != 0 is non-zero, else 0 (the union of the chosen proposals,
+ *     training.py:712-733).  masks uint8 [K][H][W], select uint8 [C][K] on the DEVICE (no host synchronisation); masks that no row selects
+ *     are not read.  16-byte accesses where the addresses are 16-byte aligned. */
+enum { LLMSEG_RESAMPLE_BILINEAR = 0, LLMSEG_RESAMPLE_BICUBIC = 1 };
+int64_t llmseg_image_resize_filter_workspace(int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, int32_t channels, int32_t filter);
+int llmseg_image_resize_u8_filter(const uint8_t* in, int64_t in_row_stride, uint8_t* out, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                                  int32_t channels, int32_t filter, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t llmseg_clip_preprocess_workspace(int32_t h, int32_t w, int32_t size);
+int llmseg_clip_preprocess(const uint8_t* in, int64_t in_row_stride, void* out, int32_t h, int32_t w, int32_t size, const float* mean, const float* std_,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int llmseg_mask_union(const uint8_t* masks, const uint8_t* select, uint8_t* out, int32_t K, int32_t C, int32_t H, int32_t W, void* stream);
 /* out[r][c] = silu(gu[r][c]) * gu[r][I + c]   (HF LlamaMLP: down(silu(gate(x)) * up(x)); gu = x.[Wgate;Wup]^T) */
 int llmseg_swiglu(const void* gu, void* out, int64_t rows, int64_t I, int64_t ldgu, int64_t ldo, void* stream);
 

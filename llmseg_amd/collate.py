@@ -203,3 +203,18 @@ def reason_seg_sample(image, image_clip, sents, gt_masks, proposal_records, devi
     if not inference:
         d["iops"] = t["sam_iops"]
     return d
+
+
+def inference_sample(image, image_clip, sents, proposals, original_size, is_sentence=True, image_path="", resize=None):
+    """The `inference=True` sample of `reason_seg_sample` for proposals that are already prepared on the device -- `proposals` is the dict of
+    `targets.proposals_and_targets_dense` (dense masks, e.g. straight from `generate_masks`) or of `targets.proposals_and_targets` (records) --
+    and no ground truth: the same questions, "[SEG]." answers and keys, `masks` an empty [0, H, W] (raw-image inference has nothing to score
+    against; `llmseg_amd/segment.py`) and no `segs_origin` (the [H, W, K] copy is the validation loops' input; the caller keeps the [K, H, W] masks)."""
+    H, W = int(original_size[0]), int(original_size[1])
+    tmpl = "\n {} Please output segmentation mask." if is_sentence else "\n What is {} in this image? Please output segmentation mask."
+    questions = [DEFAULT_IMAGE_TOKEN + tmpl.format(s.strip()) for s in sents]
+    return {"image_path": image_path, "images": image, "images_clip": image_clip,
+            "conversations": [single_turn_prompt(q, "[SEG].") for q in questions],
+            "masks": torch.zeros((0, H, W), dtype=torch.uint8), "label": None, "resize": resize, "questions": None, "sampled_classes": None,
+            "segs": proposals["sam_segs"], "ious": None, "inference": True,
+            "segs_origin": None, "bbox": proposals.get("bbox")}

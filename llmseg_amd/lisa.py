@@ -28,6 +28,7 @@ from .params import LisaConfig, ParamTree, fused_groups, init_random_, lisa_shap
 from .amg import AmgMixin
 from .generate import GenerateMixin
 from .sam_decoder import SamDecoderMixin
+from .segment import SegmentMixin
 from .trainable import TrainableMixin
 
 IMAGE_TOKEN_INDEX = -200
@@ -42,7 +43,7 @@ def _pad_rows(t, rows):
     return out
 
 
-class LISAForCausalLM(TrainableMixin, GenerateMixin, SamDecoderMixin, AmgMixin, nn.Module):
+class LISAForCausalLM(TrainableMixin, GenerateMixin, SamDecoderMixin, AmgMixin, SegmentMixin, nn.Module):
     def __init__(self, config: LisaConfig, device="cuda", **kwargs):
         super().__init__()
         # reference kwargs (model/LISA.py:150-161, training.py:140-150)

@@ -333,20 +333,73 @@ def sam_binarize(low, sel, input_size, original_size, img_size=1024, mask_thresh
     return out
 
 
-def image_resize_u8(img, out_h, out_w, crop_box=None):
-    """img uint8 [H, W, C] on the device (contiguous) -> uint8 [out_h, out_w, C]: Pillow's BILINEAR `Image.resize`, bit-identical
-    (`ResizeLongestSide.apply_image`).  crop_box = (x0, y0, x1, y1) resizes that window of img without copying it."""
+RESAMPLE = {"bilinear": 0, "bicubic": 1}        # LLMSEG_RESAMPLE_* of include/llmseg_hip.h
+
+
+def image_resize_u8(img, out_h, out_w, crop_box=None, resample="bilinear"):
+    """img uint8 [H, W, C] on the device (contiguous) -> uint8 [out_h, out_w, C]: Pillow's BILINEAR (or, resample="bicubic", BICUBIC)
+    `Image.resize`, bit-identical (`ResizeLongestSide.apply_image`; the CLIP processor's resize).  crop_box = (x0, y0, x1, y1) resizes that
+    window of img without copying it."""
     assert img.dtype == torch.uint8 and img.is_contiguous() and img.dim() == 3 and img.is_cuda
+    if resample not in RESAMPLE:
+        raise ValueError(f"resample must be one of {sorted(RESAMPLE)}, got {resample!r}")
     H, W, ch = img.shape
     x0, y0, x1, y1 = (0, 0, W, H) if crop_box is None else [int(v) for v in crop_box]
     assert 0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H
     lib = _lib.load()
-    nb = lib.llmseg_image_resize_workspace(y1 - y0, x1 - x0, int(out_h), int(out_w), ch)
-    ws = torch.empty((nb,), device=img.device, dtype=torch.uint8)
     out = torch.empty((int(out_h), int(out_w), ch), device=img.device, dtype=torch.uint8)
-    _lib.check(lib.llmseg_image_resize_u8(img.data_ptr() + (y0 * W + x0) * ch, W * ch, _ptr(out), y1 - y0, x1 - x0, int(out_h), int(out_w), ch, _ptr(ws), nb,
-                                          _stream()), "image_resize_u8")
+    if resample == "bilinear":
+        nb = lib.llmseg_image_resize_workspace(y1 - y0, x1 - x0, int(out_h), int(out_w), ch)
+        ws = torch.empty((nb,), device=img.device, dtype=torch.uint8)
+        _lib.check(lib.llmseg_image_resize_u8(img.data_ptr() + (y0 * W + x0) * ch, W * ch, _ptr(out), y1 - y0, x1 - x0, int(out_h), int(out_w), ch, _ptr(ws), nb,
+                                              _stream()), "image_resize_u8")
+        return out
+    nb = lib.llmseg_image_resize_filter_workspace(y1 - y0, x1 - x0, int(out_h), int(out_w), ch, RESAMPLE[resample])
+    ws = torch.empty((max(nb, 0),), device=img.device, dtype=torch.uint8)
+    _lib.check(lib.llmseg_image_resize_u8_filter(img.data_ptr() + (y0 * W + x0) * ch, W * ch, _ptr(out), y1 - y0, x1 - x0, int(out_h), int(out_w), ch,
+                                                 RESAMPLE[resample], _ptr(ws), nb, _stream()), "image_resize_u8")
     return out
+
+
+def clip_resized_size(h, w, size):
+    """(height, width) after the CLIP processor's shortest-edge resize: transformers `get_resize_output_image_size` (new_short = size,
+    new_long = int(size * long / short), Python float arithmetic)."""
+    short, long = (w, h) if w <= h else (h, w)
+    new_short, new_long = int(size), int(size * long / short)
+    return (new_long, new_short) if w <= h else (new_short, new_long)
+
+
+def clip_crop_origin(resized_h, resized_w, size):
+    """(top, left) of the processor's centre crop (`center_crop`: (resized - size) // 2 on each axis)."""
+    return (resized_h - size) // 2, (resized_w - size) // 2
+
+
+def clip_preprocess(img, size, mean, std):
+    """img uint8 [H, W, 3] on the device -> bf16 [1, 3, size, size]: `CLIPImageProcessor.preprocess` (shortest edge -> size with Pillow's
+    BICUBIC, centre crop, 1/255, (x - mean) / std); only the crop window is resampled."""
+    assert img.dtype == torch.uint8 and img.is_contiguous() and img.dim() == 3 and img.shape[2] == 3 and img.is_cuda
+    H, W = int(img.shape[0]), int(img.shape[1])
+    lib = _lib.load()
+    nb = lib.llmseg_clip_preprocess_workspace(H, W, int(size))
+    ws = torch.empty((max(nb, 0),), device=img.device, dtype=torch.uint8)
+    out = torch.empty((1, 3, int(size), int(size)), device=img.device, dtype=torch.bfloat16)
+    m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(lib.llmseg_clip_preprocess(_ptr(img), W * 3, _ptr(out), H, W, int(size), C.cast(m3, C.c_void_p), C.cast(s3, C.c_void_p), _ptr(ws), nb, _stream()),
+               "clip_preprocess")
+    return out
+
+
+def mask_union(masks, select):
+    """masks uint8 [K, H, W], select uint8 [C, K] (or [K]) on the device -> uint8 [C, H, W] (or [H, W]): 1 where any selected mask is non-zero.
+    The selection is read on the device; masks that no row selects are not read."""
+    assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.dim() == 3 and masks.is_cuda
+    assert select.dtype == torch.uint8 and select.is_cuda and select.shape[-1] == masks.shape[0] and select.dim() in (1, 2)
+    K, H, W = masks.shape
+    sel = select.reshape(-1, K).contiguous()
+    out = torch.zeros((sel.shape[0], H, W), device=masks.device, dtype=torch.uint8)
+    if K and sel.shape[0] and H * W:
+        _lib.check(_lib.load().llmseg_mask_union(_ptr(masks), _ptr(sel), _ptr(out), K, sel.shape[0], H, W, _stream()), "mask_union")
+    return out if select.dim() == 2 else out[0]
 
 
 def sam_preprocess(img, img_size, mean, std):
