@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include <vector>
+#include "gemm_plan.h"      // the profiling tag's encoding and its kernel-class names
 #include "llmseg_hip.h"
 
 static thread_local char g_err[512] = "";
@@ -102,13 +103,10 @@ extern "C" int llmseg_prof_collect(double* total_ms, double* total_flops, int64_
     (void)hipEventElapsedTime(&t, r.a, r.b);
     ms += t;
     fl += r.flops;
-    auto& c = by_class[((r.tag[3] % 10000) / 1000) * 2 + (r.tag[3] & 1)];    // tag = split * 10000 + variant * 1000 + flags
+    const long cls = gemm_tag_class_of(r.tag[3]) * 2 + (r.tag[3] & 1), S = gemm_tag_slices(r.tag[3]);
+    auto& c = by_class[cls];
     c[0] += t; c[1] += r.flops; c[2] += 1;
-    {
-      const long S = r.tag[3] / 10000;                                      // K-slices of this call (0 / 1 = none)
-      auto& sp = split_by_class[((r.tag[3] % 10000) / 1000) * 2 + (r.tag[3] & 1)];
-      if (S > 1) { sp[0] += 1; sp[1] += S; }
-    }
+    if (S > 1) { auto& sp = split_by_class[cls]; sp[0] += 1; sp[1] += S; }
     c[3] += 2.0 * ((double)r.tag[0] * r.tag[2] + (double)r.tag[1] * r.tag[2] + (double)r.tag[0] * r.tag[1]);      // M K + N K + M N elements, 2 bytes each
     auto& e = by_shape[{r.tag[0], r.tag[1], r.tag[2], r.tag[3]}];
     e[0] += t; e[1] += r.flops; e[2] += 1;
@@ -132,11 +130,8 @@ extern "C" int llmseg_prof_collect(double* total_ms, double* total_flops, int64_
   // dominant kernel = the GEMM kernel class with the largest total time in this window
   long dom = -1;
   for (auto& kv : by_class) if (dom < 0 || kv.second[0] > by_class[dom][0]) dom = kv.first;
-  static const char* names[] = {"gemm_bf16_tn_kernel<*, ...> (register staging, 128x128)", "?", "gemm_bf16_tn_glds_kernel<*, 2, 1>", "gemm_skinny_kernel<M>", "?", "?", "gemm_bf16_tn_t160_kernel (K-sliced)", "gemm_bf16_tn_pp2_kernel<*, false>",
-                                "gemm_bf16_tn_pp_kernel<*, false, 4>", "gemm_bf16_tn_pp_kernel<*, false, 2>"};
   if (dom >= 0) {
-    const long v = dom / 2;
-    std::string nm = (v >= 0 && v < 10) ? names[v] : "?";
+    std::string nm = gemm_class_name(dom / 2);
     const size_t star = nm.find('*');
     if (star != std::string::npos) nm.replace(star, 1, (dom & 1) ? "true" : "false");
     snprintf(g_dom_name, sizeof(g_dom_name), "%s", nm.c_str());

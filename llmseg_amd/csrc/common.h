@@ -205,6 +205,19 @@ void llmseg_count_launch();
   } while (0)
 
 void llmseg_set_error(const char* fmt, ...);
+// profiling hooks (capi.cpp)
+void llmseg_prof_begin(hipStream_t s);
+void llmseg_prof_end(hipStream_t s, double flops);
+void llmseg_prof_tag(long a, long b, long c, long d);
+// library-internal entry points that gemm.hip calls and other files define
+extern "C" __attribute__((visibility("hidden"))) int llmseg_swiglu_bwd_ld(const void* gu, const void* dout, void* dgu, int64_t rows, int64_t I, int64_t ld_dout, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int llmseg_reduce_lora_normbwd(const float* slab, int S, int64_t M, int64_t N, const void* x, const void* w, void* dx, float eps,
+                                                                                int rms, const void* dres, void* la_t, int64_t la_ldt, const void* la_w0,
+                                                                                const void* la_w1, float la_alpha, const llmseg_dropout* la_drop, const float* la_part,
+                                                                                int la_S, float la_scale, int la_zero, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int llmseg_lora_down_finish(const float* part, int S, void* y, int64_t ldy, int64_t M, float scale, int zero_cols, int nb, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int llmseg_attn_delta128(const void* O, int64_t ldo, const void* dO, int64_t lddo, float* delta, int64_t batch, int32_t heads,
+                                                                          int64_t T, void* stream);
 #define LL_CHECK(cond, ...)                 \
   do {                                      \
     if (!(cond)) {                          \

@@ -14,6 +14,7 @@
 //   R  gemm_bf16_tn_kernel       128 x 128 tile, global -> VGPR -> LDS staging (double-buffered); any K % 8 == 0, zero-filled K
 //                                tail, and the transposed-operand layouts of the backward pass.
 // Beside them gemm_skinny_kernel (V: M <= 8 rows, a weight stream without MFMA) and the reduce launches of K-sliced products (splitk_reduce*).
+// Which of them a call takes is decided in gemm_plan.h (host-only: gemm_plan), pinned by tests/golden/gemm_plans.txt; gemm_dispatch below only launches the plan.
 // LDS-DMA (global_load_lds_dwordx4) writes LDS linearly (wave-uniform base + lane*16), so the XOR swizzle that makes the
 // ds_read_b128 fragment loads conflict-free on gfx950's 16-lane service groups is applied to the per-lane SOURCE address
 // (lane -> LDS slot (row, cpos) -> global chunk cpos ^ ((row>>1)&7) of that row; the 8 lanes of a row still read one 128-byte
@@ -27,6 +28,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "llmseg_hip.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -926,7 +928,6 @@ __global__ __launch_bounds__(NTB, 2) void gemm_bf16_tn_pp2_kernel(GemmP p) {
 //   The ring's ordering rules are Q2's: tile t + 2 goes into the buffer tile t - 1 was read from, A0 + W0 in phase A, W1 + A1 in phase B (each region
 //   >= 2 phases after its last read), and phase B's wait retires tile t + 1 before the barrier that precedes its first reads.
 // Split-K only (p.kt_total > 0, no extension tile: the dispatch runs the extension product as a slab of its own), K % 64 == 0, >= 2 K-tiles per slice.
-constexpr int T160_BM = 160;
 #define T160_BL(rs, dst, voff, tt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(dst), 16, voff, (int)((tt) * (BK * 2)), 0, 0)
 #define T160_ISSUE_A0(tt, base) T160_BL(rsrc_a, (base) + a_lds0, a_off0, tt)
 #define T160_ISSUE_A1(tt, base)                                       \
@@ -1399,115 +1400,147 @@ __global__ __launch_bounds__(256) void splitk_reduce_delta_kernel(GemmP p, const
   }
 }
 
-// The kernel of one product.  The numeric values are those of the tuning knob (llmseg_gemm_set_variant; tests and tools pass them as integers).
-enum GemmKernel {
-  K_REG = 0,       // R: register staging 128 x 128 (any layout, any K % 8 == 0)
-  K_GLDS = 2,      // G: LDS-DMA 128 x 128
-  K_AUTO = 5,      // the cost model decides (never launched)
-  K_PP256 = 8,     // Q: ping-pong 256 x 256
-  K_PP128 = 9,     // Q2: two-phase 128 x 256
-  K_T160 = 10,     // T: two-phase 160 x 256, K-slices only
-};
-inline bool is_pp(GemmKernel k) { return k == K_PP256 || k == K_PP128 || k == K_T160; }      // the 8-wave LDS-DMA tiles, 256 columns wide, one workgroup per CU
-inline int pp_rows(GemmKernel k) { return k == K_PP256 ? 256 : k == K_T160 ? T160_BM : 128; }
-inline GemmKernel kernel_of_knob(int v) { return v == K_REG || v == K_GLDS || is_pp((GemmKernel)v) ? (GemmKernel)v : K_AUTO; }      // unknown value -> cost model
-
-// one launch of the 256-row or the 128-row ping-pong tile: the two kernels take the same template arguments
-template <bool OUT_F32, bool EXT, int FX = FX_NONE>
-void launch_pp(GemmKernel k, const GemmP& p, dim3 grid, hipStream_t s) {
-  if (k == K_PP256) LL_LAUNCH_KERNEL((gemm_bf16_tn_pp_kernel<OUT_F32, EXT, FX>), grid, dim3(NTB), 0, s, p);
-  else LL_LAUNCH_KERNEL((gemm_bf16_tn_pp2_kernel<OUT_F32, EXT, FX>), grid, dim3(NTB), 0, s, p);
+// the tile kernels by their template arguments: all of them take GemmP alone
+using TileKernel = void (*)(GemmP);
+template <bool OUT_F32, bool EXT, int FX = FX_NONE>      // the 256-row and the 128-row ping-pong tile take the same template arguments
+TileKernel pp_kernel(GemmKernel k) { return k == K_PP256 ? gemm_bf16_tn_pp_kernel<OUT_F32, EXT, FX> : gemm_bf16_tn_pp2_kernel<OUT_F32, EXT, FX>; }
+TileKernel reg_kernel(bool f, bool ta, bool tw) {
+  static const TileKernel k[8] = {gemm_bf16_tn_kernel<false, false, false>, gemm_bf16_tn_kernel<false, false, true>, gemm_bf16_tn_kernel<false, true, false>,
+                                  gemm_bf16_tn_kernel<false, true, true>, gemm_bf16_tn_kernel<true, false, false>, gemm_bf16_tn_kernel<true, false, true>,
+                                  gemm_bf16_tn_kernel<true, true, false>, gemm_bf16_tn_kernel<true, true, true>};
+  return k[(f ? 4 : 0) | (ta ? 2 : 0) | (tw ? 1 : 0)];
 }
-
-// The fused tail of one llmseg_gemm_bf16 call: the work the caller wants behind the product (a second output, or a pointwise pass over C), with its operands in
-// the caller's own argument struct.  The entry function fills one and hands it to gemm_dispatch, which sets `done` when the K-sliced reduce launch (NORM / NB /
-// DL) or the fused-epilogue kernel (FX) did that work; otherwise the entry function runs the launches the tail stands for.  A dispatch without a tail (the
-// extension product's own launches) fuses nothing.
-enum TailKind {
-  TAIL_NORM,       // llmseg_gemm_args.norm_out: RMSNorm(C) * norm_w
-  TAIL_NB,         // .nb_x: C = norm_bwd(product [+ LoRA term]) + nb_dres
-  TAIL_DL,         // .dl_o: delta = rowsum(dO * O) per head
-  TAIL_FX,         // .fx: RoPE / SwiGLU / SwiGLU backward in the epilogue
-};
-struct GemmTail { TailKind kind; const llmseg_gemm_args* req; bool done; };
-
+#define LL_SKINNY4(AT, SK) {gemm_skinny_kernel<1, AT, SK>, gemm_skinny_kernel<2, AT, SK>, gemm_skinny_kernel<4, AT, SK>, gemm_skinny_kernel<8, AT, SK>}
+void (*const skinny_kernel[3][2][4])(GemmP, int) = {{LL_SKINNY4(0, false), LL_SKINNY4(0, true)}, {LL_SKINNY4(1, false), LL_SKINNY4(1, true)},      // [A-row transform][K split among
+                                                    {LL_SKINNY4(2, false), LL_SKINNY4(2, true)}};                                                // the waves][rows 1, 2, 4, 8]
+#undef LL_SKINNY4
+// The product as S K-slices: slice s reads A / W columns [s q 64, ...) and writes fp32 slab s of [S][M][N] at `slabs`; the epilogue moves to the reduce launch.
+// The slices are the batch index of the ping-pong tiles (pp), the inner batch index of the register-staging kernel (the call's own moves to the outer slot).
+GemmP sliced(const GemmP& p, int S, void* slabs, bool pp, bool ta, bool tw) {
+  GemmP ps = p;
+  const int q = ((p.K + BK - 1) / BK + S - 1) / S;
+  ps.K = q * BK; ps.batch1 = S; ps.sA = ta ? (long)q * BK * p.lda : (long)q * BK; ps.sW = tw ? (long)q * BK * p.ldw : (long)q * BK;
+  if (pp) { ps.kt_total = p.K / BK; ps.sA2 = ps.sW2 = ps.sC2 = 0; ps.A2 = ps.W2 = nullptr; }
+  else { ps.k_split_total = p.K; ps.sA2 = p.sA; ps.sW2 = p.sW; ps.sC2 = (long)S * p.M * p.N; }
+  ps.C = slabs; ps.ldc = p.N; ps.sC = (long)p.M * p.N;
+  ps.bias = ps.gamma = ps.res = nullptr; ps.ldr = 0; ps.alpha = 1.f; ps.act = LLMSEG_ACT_NONE; ps.accum = 0; ps.c_vec = 1; ps.r_vec = 0; ps.b_vec = 1;
+  return ps;
+}
+// The caller's fused tail (GemmTailKind, gemm_plan.h), its operands in the caller's own struct; gemm_dispatch sets `done` when the plan had the call do that work.
+struct GemmTail { GemmTailKind kind; const llmseg_gemm_args* req; bool done; };
+static_assert(GEMM_BK == BK && GEMM_BN == BN && GEMM_ACT_NONE == LLMSEG_ACT_NONE && GEMM_FX_ROPE == LLMSEG_FX_ROPE && GEMM_FX_SWIGLU == LLMSEG_FX_SWIGLU, "gemm_plan.h restates these");
 }  // namespace
-
-// profiling hooks (capi.cpp)
-void llmseg_prof_begin(hipStream_t s);
-void llmseg_prof_end(hipStream_t s, double flops);
-void llmseg_prof_tag(long a, long b, long c, long d);
-
-// tuning knob (tools/gemm_bench.py): bits 0-3 kernel (a GemmKernel value; 10 needs a forced slice count; anything else = 5, the default = cost model),
-// bits 4-7 = XCD skew + 1, bits 8-12 = forced split-K slice count for 8 / 9 / 10.  Higher bits are ignored.
-static int g_gemm_variant = K_AUTO, g_gemm_skew = 13, g_gemm_split = 0;
-static const bool g_gemm_t160 = getenv("LLMSEG_GEMM_NO_T160") == nullptr;      // A/B switch: no 160 x 256 K-slice plans in the cost model
-static const int g_gemm_rsplit = getenv("LLMSEG_GEMM_NO_RSPLIT") ? 0 : 1;      // K-slices for the register-staging kernel (A/B switch)
 static int num_cus() {
   static int n = [] { int dev = 0, v = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v > 0 ? v : 256; }();
   return n;
 }
-extern "C" int llmseg_gemm_set_variant(int v) {
-  g_gemm_variant = v & 15;
-  if ((v >> 4) & 15) g_gemm_skew = ((v >> 4) & 15) - 1;
-  g_gemm_split = (v >> 8) & 31;
+extern "C" int llmseg_gemm_set_variant(int v) { gemm_set_variant(v); return LLMSEG_OK; }      // tuning knob (tools/gemm_bench.py): GemmKnobs' first three
+// Checks the call, builds GemmP and the query, asks gemm_plan (gemm_plan.h) and launches what the plan says.  tail: the caller's fused tail (see GemmTail), or nullptr
+static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, GemmTail* tail) {
+  LL_CHECK(a && a->struct_size == sizeof(*a), "%s: ABI mismatch: caller's struct_size %u != %zu (bind against include/llmseg_hip.h version %d)",
+           "gemm", a ? a->struct_size : 0u, sizeof(*a), LLMSEG_ABI_VERSION);
+  LL_CHECK(a && a->A && a->W && a->C, "gemm: null pointer");
+  LL_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "gemm: bad shape M=%ld N=%ld K=%ld", (long)a->M, (long)a->N, (long)a->K);
+  const bool ta = a->trans_a != 0, tw = a->trans_w != 0;
+  LL_CHECK((a->lda & 7) == 0 && (a->ldw & 7) == 0, "gemm: lda/ldw must be multiples of 8 (lda=%ld ldw=%ld)", (long)a->lda, (long)a->ldw);
+  // a K-contiguous operand is read in 16-byte chunks: K % 8 == 0, or its rows are padded (ld >= roundup8(K)) with ZEROS
+  const long k8 = (a->K + 7) & ~7L;
+  LL_CHECK((ta || (a->K & 7) == 0 || a->lda >= k8) && (tw || (a->K & 7) == 0 || a->ldw >= k8),
+           "gemm: K=%ld is not a multiple of 8 and the K-contiguous operand is not padded", (long)a->K);
+  LL_CHECK((!ta || a->lda >= a->M) && (!tw || a->ldw >= a->N), "gemm: transposed operand needs ld >= rows");
+  LL_CHECK((((uintptr_t)a->A) & 15) == 0 && (((uintptr_t)a->W) & 15) == 0, "gemm: A/W must be 16-byte aligned");
+  LL_CHECK(((a->strideA | a->strideW | a->strideA2 | a->strideW2) & 7) == 0, "gemm: batch strides of A/W must be multiples of 8");
+  LL_CHECK(!a->accumulate || a->out_f32, "gemm: accumulate needs fp32 output");
+  LL_CHECK(!a->A2 || (a->W2 && (a->lda2 & 7) == 0 && (a->ldw2 & 7) == 0 && a->lda2 >= 64 && a->ldw2 >= 64 && (((uintptr_t)a->A2 | (uintptr_t)a->W2) & 15) == 0),
+           "gemm: bad extension operands (A2 [M][64], W2 [N][64], 16-byte aligned rows)");
+  LL_CHECK((!a->a_norm_w || (((uintptr_t)a->a_norm_w) & 15) == 0) && (!a->a_swiglu || a->lda >= 2 * a->K),
+           "gemm: a_norm_w must be 16-byte aligned, a_swiglu needs [gate | up] rows (lda >= 2 K)");
+  const int esz = a->out_f32 ? 4 : 2;
+  GemmP p;
+  p.A = (const bf16_t*)a->A; p.W = (const bf16_t*)a->W; p.C = a->C;
+  p.bias = (const bf16_t*)a->bias; p.gamma = (const bf16_t*)a->gamma; p.res = (const bf16_t*)a->residual;
+  p.M = (int)a->M; p.N = (int)a->N; p.K = (int)a->K;
+  p.lda = a->lda; p.ldw = a->ldw; p.ldc = a->ldc; p.ldr = a->residual ? a->ldr : 0;
+  const long batch1 = a->batch > 0 ? a->batch : 1, batch2 = a->batch2 > 0 ? a->batch2 : 1;
+  const long batch = batch1 * batch2;
+  p.batch1 = (int)batch1;
+  p.sA = a->strideA; p.sW = a->strideW; p.sC = a->strideC;
+  p.sA2 = a->strideA2; p.sW2 = a->strideW2; p.sC2 = a->strideC2;
+  p.alpha = a->alpha; p.act = a->act;
+  p.kt_total = 0; p.k_split_total = 0; p.accum = a->accumulate ? 1 : 0;
+  p.fx = 0; p.fx_T = a->fx_T; p.fx_cols = (int)a->fx_cols; p.fx_I = a->fx == LLMSEG_FX_SWIGLU ? (int)(a->N / 2) : (int)a->N;
+  p.fx_cos = a->fx_cos; p.fx_sin = a->fx_sin; p.fx_out = (bf16_t*)a->fx_out; p.fx_in = (const bf16_t*)a->fx_in; p.fx_ld = a->fx_ld;
+  // vector stores/loads need 4-element alignment of every row start; otherwise the kernel goes element-wise
+  p.c_vec = ((((uintptr_t)a->C) % (4 * esz)) == 0 && (a->ldc & 3) == 0 && ((a->strideC | a->strideC2) & 3) == 0) ? 1 : 0;
+  p.r_vec = (p.res && (((uintptr_t)p.res) & 7) == 0 && (p.ldr & 3) == 0 && ((a->strideC | a->strideC2) & 3) == 0) ? 1 : 0;
+  p.b_vec = ((p.bias == nullptr || (((uintptr_t)p.bias) & 7) == 0) && (p.gamma == nullptr || (((uintptr_t)p.gamma) & 7) == 0)) ? 1 : 0;
+  p.A2 = (const bf16_t*)a->A2; p.W2 = (const bf16_t*)a->W2; p.lda2 = a->lda2; p.ldw2 = a->ldw2;
+  p.a_norm_w = (const bf16_t*)a->a_norm_w; p.a_norm_eps = a->a_norm_eps; p.a_swiglu = a->a_swiglu;
+  const llmseg_gemm_args* r = tail ? tail->req : nullptr;
+  GemmQuery q;      // what gemm_plan reads of the call
+  q.M = p.M; q.N = p.N; q.K = p.K; q.batch1 = batch1; q.batch2 = batch2; q.trans_a = ta; q.trans_w = tw; q.out_f32 = a->out_f32 != 0; q.act = p.act; q.alpha_one = p.alpha == 1.f;
+  q.bias = p.bias != nullptr; q.gamma = p.gamma != nullptr; q.residual = p.res != nullptr; q.ext = p.A2 != nullptr; q.a_norm = p.a_norm_w != nullptr; q.a_swiglu = p.a_swiglu != 0;
+  q.ldc = p.ldc; q.ldr = p.ldr; q.ldn = r ? r->ldn : 0; q.stride_c = p.sC; q.tail = tail ? tail->kind : TAIL_NONE; q.fx = a->fx; q.ncu = num_cus();
+  q.ws = a->workspace != nullptr; q.ws_aligned = (((uintptr_t)a->workspace) & 15) == 0; q.ws_bytes = a->workspace_bytes;
+  q.norm_ptrs_aligned = r && ((((uintptr_t)p.C) | ((uintptr_t)p.res) | ((uintptr_t)r->norm_w) | ((uintptr_t)r->norm_out)) & 15) == 0;
+  const GemmKnobs& knobs = gemm_knobs();
+  const GemmPlan pl = gemm_plan(q, knobs);
+  LL_CHECK(pl.route != ROUTE_REFUSED, "gemm: %s (M=%ld N=%ld K=%ld)", pl.refusal, (long)a->M, (long)a->N, (long)a->K);
+  p.skew = knobs.skew; p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.group_m = pl.group_m;
+  if (pl.ext == EXT_SECOND || pl.ext == EXT_SLAB) {
+    // the extension product as a K = 64 call of its own.  No tail: the caller's belongs to the whole product (after both calls, the entry function runs it)
+    llmseg_gemm_args g1 = *a, g2 = *a;
+    g2.A = a->A2; g2.W = a->W2; g2.lda = a->lda2; g2.ldw = a->ldw2; g2.K = 64; g2.bias = nullptr; g1.A2 = g1.W2 = g2.A2 = g2.W2 = nullptr;
+    if (pl.ext == EXT_SECOND) {      // C = epi(alpha * A.W^T + bias + residual), then C = epi(alpha * A2.W2^T + C)
+      g2.residual = a->C; g2.ldr = a->ldc;
+      const int rc = gemm_dispatch(&g1, stream, nullptr);
+      return rc != LLMSEG_OK ? rc : gemm_dispatch(&g2, stream, nullptr);
+    }
+    // one more fp32 slab behind the slices', summed by the reduce launch
+    g2.gamma = g2.residual = nullptr; g2.alpha = 1.f; g2.act = LLMSEG_ACT_NONE; g2.out_f32 = 1; g2.accumulate = 0;
+    g2.C = (float*)a->workspace + (long)pl.slices * p.M * p.N; g2.ldc = p.N; g2.workspace = nullptr; g2.workspace_bytes = 0;
+    const int rc = gemm_dispatch(&g2, stream, nullptr);
+    if (rc != LLMSEG_OK) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  llmseg_prof_begin(s); llmseg_prof_tag(p.M, p.N, p.K, pl.tag);
+  const bool f = q.out_f32, pp = pl.route == ROUTE_PP || pl.route == ROUTE_PP_SLICED, slices = pl.route == ROUTE_REG_SLICED || pl.route == ROUTE_PP_SLICED;
+  const float* slabs = (const float*)a->workspace;
+  const int S2 = pl.slices + (pl.ext == EXT_SLAB ? 1 : 0);      // slabs the reduce launch sums
+  if (pl.route == ROUTE_SKINNY) {
+    const auto k = skinny_kernel[p.a_norm_w ? 1 : p.a_swiglu ? 2 : 0][pl.skinny_ksplit][pl.skinny_rows == 8 ? 3 : pl.skinny_rows >> 1];
+    LL_LAUNCH_KERNEL(k, dim3((unsigned)(pl.skinny_ksplit ? (p.N + 3) / 4 : (p.N + 15) / 16)), dim3(256), 0, s, p, f ? 1 : 0);
+  } else {
+    // the tile kernel: its K-slices are the grid's y beside the batch index (register staging) or instead of it (ping-pong: batch == 1)
+    GemmP t = slices ? sliced(p, pl.slices, a->workspace, pp, ta, tw) : p;
+    TileKernel k = pl.route == ROUTE_GLDS ? (f ? gemm_bf16_tn_glds_kernel<true> : gemm_bf16_tn_glds_kernel<false>) : reg_kernel(f || slices, ta, tw);
+    if (pl.route == ROUTE_PP_SLICED) k = pl.kernel == K_T160 ? gemm_bf16_tn_t160_kernel : pp_kernel<true, false>(pl.kernel);
+    else if (pl.fx_fused) {
+      t.fx = a->fx;
+      if (a->fx == LLMSEG_FX_SWIGLU_BWD) t.C = (bf16_t*)a->C - a->N;      // gemm_fx pointed C at the up half for the two-launch route: back to the row start
+      k = a->fx == LLMSEG_FX_ROPE ? pp_kernel<false, true, FX_ROPE>(pl.kernel) : a->fx == LLMSEG_FX_SWIGLU ? pp_kernel<false, false, FX_SWIGLU>(pl.kernel) : pp_kernel<false, false, FX_SWIGLU_BWD>(pl.kernel);
+    } else if (pp) k = p.A2 ? pp_kernel<false, true>(pl.kernel) : f ? pp_kernel<true, false>(pl.kernel) : pp_kernel<false, false>(pl.kernel);      // extension: bf16 out only
+    LL_LAUNCH_KERNEL(k, dim3(p.tiles_m * p.tiles_n, (unsigned)((slices ? pl.slices : 1) * batch)), dim3(pp ? NTB : NT), 0, s, t);
+  }
+  // the reduce launch of a K-sliced product: sums the slabs and applies p's epilogue; a workgroup-per-row kernel where the caller's tail rides in it
+#define LL_ROW_REDUCE(kernel, ...) LL_LAUNCH_KERNEL((pl.cpt == 1 ? kernel<1> : pl.cpt == 2 ? kernel<2> : kernel<4>), dim3((unsigned)p.M), dim3(256), 0, s, p, slabs, S2, __VA_ARGS__)
+  if (pl.reduce == REDUCE_DL) LL_ROW_REDUCE(splitk_reduce_delta_kernel, (const bf16_t*)r->dl_o, (long)r->dl_ldo, r->dl_out, (int)r->dl_heads, (int)r->dl_T);
+  else if (pl.reduce == REDUCE_NORM) LL_ROW_REDUCE(splitk_reduce_rmsnorm_kernel, (const bf16_t*)r->norm_w, r->norm_eps, (bf16_t*)r->norm_out, (long)r->ldn);
+  else if (pl.reduce == REDUCE_NB) {
+    const int rc = llmseg_reduce_lora_normbwd(slabs, S2, p.M, p.N, r->nb_x, r->nb_w, r->C, r->nb_eps, r->nb_rms, r->nb_dres, (void*)r->nb_lora_t, r->nb_lora_ldt, r->nb_lora_w0,
+                                              r->nb_lora_w1, r->nb_lora_alpha, (const llmseg_dropout*)r->nb_lora_drop, r->nb_lora_part, r->nb_lora_S, r->nb_lora_scale,
+                                              r->nb_lora_zero, stream);
+    if (rc != LLMSEG_OK) return rc;
+  } else if (pl.reduce == REDUCE_PLAIN) {
+    const unsigned rg = (unsigned)std::min<long>(((long)p.M * (p.N >> 2) + 255) / 256, 4096);
+    LL_LAUNCH_KERNEL(splitk_reduce_kernel, dim3(rg, (unsigned)batch), dim3(256), 0, s, p, slabs, S2, f ? 1 : 0);
+  }
+#undef LL_ROW_REDUCE
+  if (pl.tail_done) tail->done = true;
+  llmseg_prof_end(s, 2.0 * (double)a->M * (double)a->N * (double)a->K * (double)batch);
+  LL_LAUNCH_CHECK("gemm_bf16_tn");
   return LLMSEG_OK;
 }
-
-namespace {
-// Cost model of the K % 64 == 0 kernels (microseconds; constants fitted to tools/gemm_bench.py on MI355X, profiles/r02*_gemm*.txt).
-// One ping-pong workgroup owns a CU: a K-tile of the 256 x 256 kernel takes ~1.7 us (1.25 PF/s over 256 CUs), of the 128 x 256
-// kernel ~1.0 us; prologue + epilogue ~7 / 4.5 us.  The 128 x 128 kernel shares a CU between up to 4 workgroups (2.4 us per K-tile
-// each when all four are resident, latency-bound 1.3 us when alone).
-struct GemmPlan { GemmKernel kernel; int split; double us; };
-// bm = the tile's rows: 256 / 128 / 160.  The 160 x 256 kernel competes for K-slice plans only.  Its K-tile measures ~1.3 x the 128-row one (slope of
-// the per-call time over the 638-row shapes, profiles/r07a_gemm_t160.txt), but 4 x 16 x 4 = 256 workgroups fill every CU where 5 x 16 x 3 left 16 idle,
-// and on all five N = 4096 shapes 160 x 256 x 4 slices beats 128 x 256 x 3 by 5-13 % per call: 1.13 is the price that reproduces that ordering.
-constexpr double T160_KT_US = 1.13;
-inline double pp_cost(long M, long N, int nt, int bm, int S, long ncu, bool f32out) {
-  const long tiles = ((M + bm - 1) / bm) * ((N + 255) / 256);
-  const long rounds = (tiles * S + ncu - 1) / ncu;
-  const int q = (nt + S - 1) / S;
-  // (round 5: re-fitting these constants to the two-phase kernel from two isolated shapes -- 0.8 + 6.4 / 1.64 + 4.5 -- moved the K-slice plans of
-  // the Llama N = 4096 shapes and cost 4 % at 2 images, 6 % at 24: measured and reverted, profiles/r05g_gemm_dispatch.md)
-  const double it = bm == 256 ? 1.7 : bm == 160 ? T160_KT_US : 1.0, fix = (bm == 256 ? 7.0 : 4.5) + ((S > 1 || f32out) ? 1.0 : 0.0);
-  // Round 5: without K-slices a partially filled last round is priced at 0.5 + 0.5 x its fill instead of a whole round -- a CU that shares the
-  // fabric with fewer neighbours fetches its operands faster (measured, tools/gemm_bench.py at the 2-image shapes: 8192 x 1280 x 1280 on 160
-  // workgroups of 256 x 256 takes 35 us, not 41; the whole-round price made the 128 x 256 tile win SAM proj / lin1 / q|k|v-windows, where the
-  // 256 x 256 tile measures +9 / +6 / +5 %).  K-sliced plans keep the whole-round price their slice counts were tuned with.
-  double eff_rounds = (double)rounds;
-  if (S == 1) {
-    const long full = tiles / ncu, rem = tiles - full * ncu;
-    eff_rounds = (double)full + (rem ? 0.5 + 0.5 * (double)rem / (double)ncu : 0.0);
-  }
-  double us = eff_rounds * (q * it + fix);
-  if (S > 1) us += 2.5 + ((double)(S + 1) * M * N * 4.0) / 4.0e6;     // reduce launch: slabs read once (mostly from the Infinity Cache)
-  return us;
-}
-inline double glds_cost(long M, long N, int nt, long ncu) {
-  const long tiles = ((M + 127) / 128) * ((N + 127) / 128);
-  const long full = tiles / (4 * ncu), rem = tiles - full * 4 * ncu;
-  double us = (double)full * (nt * 2.4 + 4.0);
-  if (rem > 0) { const double w = (double)((rem + ncu - 1) / ncu); us += nt * std::max(1.3, 0.6 * w) + 4.0; }
-  return us;
-}
-inline bool split_ok(int nt, int S) {       // every slice needs >= 2 K-tiles (the kernel's pipeline depth)
-  if (S <= 1) return S == 1;
-  const int q = (nt + S - 1) / S;
-  return q >= 2 && nt - (S - 1) * q >= 2;
-}
-}  // namespace
-
-static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, GemmTail* tail);
-
-extern "C" int llmseg_norm(const void* x, const void* w, const void* b, void* y, int64_t rows, int64_t cols, int64_t ldx, int64_t ldy, float eps, int rms,
-                           const int32_t* row_map, void* stream);
-
-extern "C" int llmseg_rope(void* x, const float* cos, const float* sin, int64_t rows, int64_t T, int32_t heads, int32_t head_dim, int64_t ld, void* stream);
-extern "C" int llmseg_swiglu(const void* gu, void* out, int64_t rows, int64_t I, int64_t ldgu, int64_t ldo, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int llmseg_swiglu_bwd_ld(const void* gu, const void* dout, void* dgu, int64_t rows, int64_t I, int64_t ld_dout, void* stream);
-
-static const bool g_fx_off = getenv("LLMSEG_GEMM_NO_FX") != nullptr;      // A/B switch: always the GEMM + pointwise launch
 
 // llmseg_gemm_args.fx: the fused kernel where the call takes the 128 x 256 two-phase kernel in one K-slice (the Llama layer at 2 images per micro-step),
 // the GEMM followed by the pointwise launch it replaces everywhere else.  Same bits either way.
@@ -1530,24 +1563,13 @@ static int gemm_fx(const llmseg_gemm_args* a, void* stream) {
   llmseg_gemm_args g = *a;
   if (a->fx == LLMSEG_FX_SWIGLU_BWD) g.C = (bf16_t*)a->C + a->N;      // unfused route: d(out) lands in the up half of C's rows, llmseg_swiglu_bwd then works in place
   GemmTail tail{TAIL_FX, a, false};
-  const int rc = gemm_dispatch(&g, stream, g_fx_off ? nullptr : &tail);
+  const int rc = gemm_dispatch(&g, stream, &tail);
   if (rc != LLMSEG_OK || tail.done) return rc;
   if (a->fx == LLMSEG_FX_ROPE) return llmseg_rope(a->C, a->fx_cos, a->fx_sin, a->M, a->fx_T, (int32_t)(a->fx_cols / 128), 128, a->ldc, stream);
   if (a->fx == LLMSEG_FX_SWIGLU) return llmseg_swiglu(a->C, a->fx_out, a->M, a->N / 2, a->ldc, a->fx_ld, stream);
   LL_CHECK(a->fx_ld == 2 * a->N && a->ldc == 2 * a->N, "gemm: fx swiglu_bwd on this shape (two-launch route) needs dense gate|up and d(gate|up) rows");
   return llmseg_swiglu_bwd_ld(a->fx_in, g.C, a->C, a->M, a->N, a->ldc, stream);
 }
-
-extern "C" __attribute__((visibility("hidden"))) int llmseg_reduce_lora_normbwd(const float* slab, int S, int64_t M, int64_t N, const void* x, const void* w, void* dx, float eps,
-                                                                                int rms, const void* dres, void* la_t, int64_t la_ldt, const void* la_w0,
-                                                                                const void* la_w1, float la_alpha, const llmseg_dropout* la_drop, const float* la_part,
-                                                                                int la_S, float la_scale, int la_zero, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int llmseg_lora_down_finish(const float* part, int S, void* y, int64_t ldy, int64_t M, float scale, int zero_cols, int nb, void* stream);
-extern "C" int llmseg_norm_bwd_add(const void* dy, const void* x, const void* w, const void* dres, void* dx, float* dw, float* db, int64_t rows, int64_t cols,
-                                   float eps, int rms, void* workspace, int64_t workspace_bytes, void* stream);
-extern "C" int llmseg_lora_apply(void* y, int64_t ldy, const void* xa, int64_t ldxa, const void* w0, const void* w1, int64_t M, int64_t N, int32_t w_rn,
-                                 float alpha, const llmseg_dropout* drop, void* stream);
-static const bool g_nb_off = getenv("LLMSEG_GEMM_NO_NB") != nullptr;      // A/B switch: always the product + lora_apply + norm_bwd launches
 
 // llmseg_gemm_args.nb_x: C = norm_bwd(dy = the bf16 product [+ LoRA term], nb_x, nb_w) + nb_dres.  K-sliced products fold all of it into their reduce launch;
 // every other route writes the product to the tail of the caller's workspace and runs llmseg_lora_apply / llmseg_norm_bwd_add behind it.  Same bits.
@@ -1567,7 +1589,7 @@ static int gemm_nb(const llmseg_gemm_args* a, void* stream) {
   g.C = tmp;                                                  // the two-launch routes leave the bf16 product here; the fused tail writes a->C itself
   g.nb_x = nullptr;
   GemmTail tail{TAIL_NB, a, false};
-  const int rc = gemm_dispatch(&g, stream, g_nb_off ? nullptr : &tail);
+  const int rc = gemm_dispatch(&g, stream, &tail);
   if (rc != LLMSEG_OK || tail.done) return rc;
   if (a->nb_lora_t && a->nb_lora_part) {          // the LoRA operand is still K-slice partials: finish them first (what the fused tail does in its own launch)
     const int rc0 = llmseg_lora_down_finish(a->nb_lora_part, a->nb_lora_S, (void*)a->nb_lora_t, a->nb_lora_ldt, a->M, a->nb_lora_scale, a->nb_lora_zero, a->nb_lora_w1 ? 2 : 1, stream);
@@ -1581,9 +1603,6 @@ static int gemm_nb(const llmseg_gemm_args* a, void* stream) {
   return llmseg_norm_bwd_add(tmp, a->nb_x, a->nb_w, a->nb_dres, a->C, nullptr, nullptr, a->M, a->N, a->nb_eps, a->nb_rms, nullptr, 0, stream);
 }
 
-extern "C" __attribute__((visibility("hidden"))) int llmseg_attn_delta128(const void* O, int64_t ldo, const void* dO, int64_t lddo, float* delta, int64_t batch, int32_t heads,
-                                                                          int64_t T, void* stream);
-
 // llmseg_gemm_args.dl_o: the product is dO of an attention (dX of o_proj) and the call also returns delta = rowsum_d(dO * O) per head: inside the reduce launch of
 // a K-sliced product, by the attention backward's own delta kernel behind the product otherwise.  Same bits.
 static int gemm_dl(const llmseg_gemm_args* a, void* stream) {
@@ -1591,11 +1610,10 @@ static int gemm_dl(const llmseg_gemm_args* a, void* stream) {
                !a->norm_out && !a->fx && !a->nb_x && !a->accumulate && a->N == (int64_t)a->dl_heads * 128 && (a->M % a->dl_T) == 0 && (a->ldc & 7) == 0 && (a->dl_ldo & 7) == 0 &&
                ((((uintptr_t)a->dl_o) | ((uintptr_t)a->C)) & 15) == 0,
            "gemm: dl_o needs a plain bf16 product of width heads x 128 over batch x T rows, 16-byte aligned rows");
-  static const bool off = getenv("LLMSEG_GEMM_NO_DL") != nullptr;      // A/B switch
   llmseg_gemm_args g = *a;
   g.dl_o = nullptr;
   GemmTail tail{TAIL_DL, a, false};
-  const int rc = gemm_dispatch(&g, stream, off ? nullptr : &tail);
+  const int rc = gemm_dispatch(&g, stream, &tail);
   if (rc != LLMSEG_OK || tail.done) return rc;
   return llmseg_attn_delta128(a->dl_o, a->dl_ldo, a->C, a->ldc, a->dl_out, a->M / a->dl_T, a->dl_heads, a->dl_T, stream);
 }
@@ -1609,284 +1627,8 @@ extern "C" int llmseg_gemm_bf16(const llmseg_gemm_args* a, void* stream) {
   LL_CHECK(a->norm_w && !a->out_f32 && a->batch <= 1 && a->batch2 <= 1 && (a->N & 7) == 0 && (a->ldn & 7) == 0 && a->ldn >= a->N && (a->ldc & 7) == 0 &&
                ((((uintptr_t)a->norm_w) | ((uintptr_t)a->norm_out) | ((uintptr_t)a->C)) & 15) == 0 && !a->accumulate,
            "gemm: norm_out needs norm_w, bf16 output, batch 1, N, ldc and ldn multiples of 8, 16-byte aligned pointers");
-  static const bool no_fuse = getenv("LLMSEG_GEMM_NO_NORM_FUSE") != nullptr;      // A/B switch: always the two-launch route
   GemmTail tail{TAIL_NORM, a, false};
-  const int rc = gemm_dispatch(a, stream, no_fuse ? nullptr : &tail);
+  const int rc = gemm_dispatch(a, stream, &tail);
   if (rc != LLMSEG_OK || tail.done) return rc;
   return llmseg_norm(a->C, a->norm_w, nullptr, a->norm_out, a->M, a->N, a->ldc, a->ldn, a->norm_eps, 1, nullptr, stream);
-}
-
-// tail: the caller's fused tail (see GemmTail), or nullptr
-static int gemm_dispatch(const llmseg_gemm_args* a, void* stream, GemmTail* tail) {
-  LL_CHECK(a && a->struct_size == sizeof(*a), "%s: ABI mismatch: caller's struct_size %u != %zu (bind against include/llmseg_hip.h version %d)",
-           "gemm", a ? a->struct_size : 0u, sizeof(*a), LLMSEG_ABI_VERSION);
-  LL_CHECK(a && a->A && a->W && a->C, "gemm: null pointer");
-  LL_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "gemm: bad shape M=%ld N=%ld K=%ld", (long)a->M, (long)a->N, (long)a->K);
-  const bool ta = a->trans_a != 0, tw = a->trans_w != 0;
-  LL_CHECK((a->lda & 7) == 0 && (a->ldw & 7) == 0, "gemm: lda/ldw must be multiples of 8 (lda=%ld ldw=%ld)", (long)a->lda, (long)a->ldw);
-  // a K-contiguous operand is read in 16-byte chunks: K % 8 == 0, or its rows are padded (ld >= roundup8(K)) with ZEROS
-  const long k8 = (a->K + 7) & ~7L;
-  LL_CHECK((ta || (a->K & 7) == 0 || a->lda >= k8) && (tw || (a->K & 7) == 0 || a->ldw >= k8),
-           "gemm: K=%ld is not a multiple of 8 and the K-contiguous operand is not padded", (long)a->K);
-  LL_CHECK((!ta || a->lda >= a->M) && (!tw || a->ldw >= a->N), "gemm: transposed operand needs ld >= rows");
-  LL_CHECK((((uintptr_t)a->A) & 15) == 0 && (((uintptr_t)a->W) & 15) == 0, "gemm: A/W must be 16-byte aligned");
-  LL_CHECK(((a->strideA | a->strideW | a->strideA2 | a->strideW2) & 7) == 0, "gemm: batch strides of A/W must be multiples of 8");
-  LL_CHECK(!a->accumulate || a->out_f32, "gemm: accumulate needs fp32 output");
-  const int esz = a->out_f32 ? 4 : 2;
-  GemmP p;
-  p.A = (const bf16_t*)a->A; p.W = (const bf16_t*)a->W; p.C = a->C;
-  p.bias = (const bf16_t*)a->bias; p.gamma = (const bf16_t*)a->gamma; p.res = (const bf16_t*)a->residual;
-  p.M = (int)a->M; p.N = (int)a->N; p.K = (int)a->K;
-  p.lda = a->lda; p.ldw = a->ldw; p.ldc = a->ldc; p.ldr = a->residual ? a->ldr : 0;
-  const long batch1 = a->batch > 0 ? a->batch : 1, batch2 = a->batch2 > 0 ? a->batch2 : 1;
-  const long batch = batch1 * batch2;
-  p.batch1 = (int)batch1;
-  p.sA = a->strideA; p.sW = a->strideW; p.sC = a->strideC;
-  p.sA2 = a->strideA2; p.sW2 = a->strideW2; p.sC2 = a->strideC2;
-  p.alpha = a->alpha; p.act = a->act;
-  p.kt_total = 0; p.k_split_total = 0; p.accum = a->accumulate ? 1 : 0;
-  p.fx = 0; p.fx_T = a->fx_T; p.fx_cols = (int)a->fx_cols; p.fx_I = a->fx == LLMSEG_FX_SWIGLU ? (int)(a->N / 2) : (int)a->N;
-  p.fx_cos = a->fx_cos; p.fx_sin = a->fx_sin; p.fx_out = (bf16_t*)a->fx_out; p.fx_in = (const bf16_t*)a->fx_in; p.fx_ld = a->fx_ld;
-  // vector stores/loads need 4-element alignment of every row start; otherwise the kernel goes element-wise
-  p.c_vec = ((((uintptr_t)a->C) % (4 * esz)) == 0 && (a->ldc & 3) == 0 && ((a->strideC | a->strideC2) & 3) == 0) ? 1 : 0;
-  p.r_vec = (p.res && (((uintptr_t)p.res) & 7) == 0 && (p.ldr & 3) == 0 && ((a->strideC | a->strideC2) & 3) == 0) ? 1 : 0;
-  p.b_vec = ((p.bias == nullptr || (((uintptr_t)p.bias) & 7) == 0) && (p.gamma == nullptr || (((uintptr_t)p.gamma) & 7) == 0)) ? 1 : 0;
-
-  p.skew = g_gemm_skew;
-  p.A2 = (const bf16_t*)a->A2; p.W2 = (const bf16_t*)a->W2; p.lda2 = a->lda2; p.ldw2 = a->ldw2;
-  static const int group_m_env = getenv("LLMSEG_GEMM_GROUP_M") ? atoi(getenv("LLMSEG_GEMM_GROUP_M")) : 0;   // tuning override
-  const int nt = p.K / BK;
-  const long ncu = num_cus();
-  // ---- the plan: kernel and K-slice count
-  GemmKernel kernel = (p.K % BK == 0 && !ta && !tw) ? kernel_of_knob(g_gemm_variant) : K_REG;
-  if ((kernel == K_PP256 || kernel == K_PP128) && nt < (a->A2 ? 1 : 2)) kernel = K_GLDS;
-  if (kernel == K_T160 && nt < 2) kernel = K_GLDS;        // (the extension product's own K = 64 launch under a forced 160 x 256 tile)
-  // split-K needs a dense-enough problem for the slab layout [S][M][N], 4-column alignment and room in the caller's workspace
-  const bool can_split = batch == 1 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && a->workspace != nullptr &&
-                         (((uintptr_t)a->workspace) & 15) == 0 && (!p.res || (p.ldr & 3) == 0);
-  auto ws_fits = [&](int S) { return (double)(S + (a->A2 ? 1 : 0)) * p.M * p.N * 4.0 <= (double)a->workspace_bytes; };   // + the extension product's slab
-  int split = 1;
-  if (kernel == K_AUTO) {
-    // auto: minimum of the cost model over {128 x 128 DMA kernel, ping-pong 256 x 256 / 128 x 256 with 1..16 K-slices}
-    GemmPlan best{K_GLDS, 1, glds_cost(p.M, p.N, nt, ncu) * (double)batch};
-    if (nt >= (a->A2 ? 1 : 2)) {
-      // tiles 256 x 256, 128 x 256 and -- K-slice plans only -- 160 x 256.  Not for the fused-epilogue calls, and not for products with a
-      // residual add: the forward's residual-stream projections (o_proj, down_proj) keep the 3-slice plan, so the forward pass -- every loss and the mask
-      // head's gradients, which the full-depth parity test measures against the fp32 oracle -- computes the bits it computed before; moving its fp32
-      // partial sums from 3 to 4 groups re-draws that chaotic comparison (profiles/r06_spread_fulldepth_grads_seeds3-5.md).  The backward dX products and
-      // lm_head's dX take the new tile.
-      const bool t160 = g_gemm_t160 && !a->fx && !a->residual;
-      for (const GemmKernel k : {K_PP256, K_PP128, K_T160}) {
-        if (k == K_T160 && !t160) continue;
-        const int bm = pp_rows(k);
-        for (int S = k == K_T160 ? 2 : 1; S <= 16; ++S) {
-          if (S > 1 && (!can_split || !split_ok(nt, S) || !ws_fits(S))) continue;
-          if (S > 1 && ((p.M + bm - 1) / bm) * ((p.N + 255) / 256) * S > ncu) break;     // slices only to fill ONE round of the CUs
-          const double us = pp_cost(p.M, p.N, nt, bm, S, ncu, a->out_f32 != 0) * (double)batch;
-          if (us < best.us * 0.97 || (us < best.us && S == 1)) best = GemmPlan{k, S, us};
-        }
-      }
-    }
-    kernel = best.kernel; split = best.split;
-  } else if (kernel == K_PP256 || kernel == K_PP128) {
-    split = g_gemm_split > 1 ? g_gemm_split : 1;
-    if (split > 1) LL_CHECK(can_split && split_ok(nt, split) && ws_fits(split), "gemm: forced split-K %d not possible for this call", split);
-  } else if (kernel == K_T160) {
-    split = g_gemm_split;
-    LL_CHECK(split > 1 && can_split && split_ok(nt, split) && ws_fits(split), "gemm: variant 10 (160 x 256, K-sliced) needs a forced split-K count >= 2 that is possible for this call (got %d)", split);
-  }
-  if (p.A2) {
-    // C = epi(alpha * (A.W^T + A2.W2^T)), A2 [M][64], W2 [N][64]: fused as one more K-tile of the ping-pong kernel; any other
-    // kernel runs the product as a second launch that accumulates onto C (linear epilogues only)
-    LL_CHECK(p.W2 && batch == 1 && !ta && !tw && (p.lda2 & 7) == 0 && (p.ldw2 & 7) == 0 && p.lda2 >= 64 && p.ldw2 >= 64 &&
-                 (((uintptr_t)p.A2 | (uintptr_t)p.W2) & 15) == 0, "gemm: bad extension operands (A2 [M][64], W2 [N][64], 16-byte aligned rows)");
-    LL_CHECK(!a->out_f32, "gemm: extension operands need bf16 output");
-    if (is_pp(kernel) && split > 1) {
-      // split-K: the extension product is one more fp32 slab (a K = 64 launch of its own), summed by the reduce kernel
-      llmseg_gemm_args g2 = *a;
-      g2.A = a->A2; g2.W = a->W2; g2.lda = a->lda2; g2.ldw = a->ldw2; g2.K = 64; g2.A2 = g2.W2 = nullptr;
-      g2.bias = g2.gamma = g2.residual = nullptr; g2.alpha = 1.f; g2.act = LLMSEG_ACT_NONE; g2.out_f32 = 1; g2.accumulate = 0;
-      g2.C = (float*)a->workspace + (long)split * p.M * p.N; g2.ldc = p.N; g2.workspace = nullptr; g2.workspace_bytes = 0;
-      const int rc = gemm_dispatch(&g2, stream, nullptr);        // (no tail: the caller's belongs to the whole product, not to this slab)
-      if (rc != LLMSEG_OK) return rc;
-    } else if (!is_pp(kernel)) {
-      LL_CHECK(a->act == LLMSEG_ACT_NONE && !a->gamma, "gemm: extension operands on this shape need a linear epilogue");
-      llmseg_gemm_args g1 = *a, g2 = *a;
-      g1.A2 = g1.W2 = nullptr;
-      int rc = gemm_dispatch(&g1, stream, nullptr);               // no tail: the caller's work comes after BOTH launches (the entry function runs it)
-      if (rc != LLMSEG_OK) return rc;
-      g2.A = a->A2; g2.W = a->W2; g2.lda = a->lda2; g2.ldw = a->ldw2; g2.K = 64; g2.bias = nullptr; g2.residual = a->C; g2.ldr = a->ldc;
-      g2.A2 = g2.W2 = nullptr;
-      return gemm_dispatch(&g2, stream, nullptr);
-    }
-  }
-  p.a_norm_w = (const bf16_t*)a->a_norm_w; p.a_norm_eps = a->a_norm_eps; p.a_swiglu = a->a_swiglu;
-  const bool a_xform = p.a_norm_w || p.a_swiglu;
-  LL_CHECK(!a_xform || (p.M <= 8 && !ta && !tw && batch == 1 && !p.A2 && (p.K & 7) == 0 && !(p.a_norm_w && p.a_swiglu) &&
-                        (!p.a_norm_w || (((uintptr_t)p.a_norm_w) & 15) == 0) && (!p.a_swiglu || p.lda >= 2 * p.K)),
-           "gemm: A-row transforms (a_norm_w / a_swiglu) are decode-step fusions of the M <= 8 route");
-  if (p.M <= 8 && !ta && !tw && batch == 1 && !p.A2 && (p.K & 7) == 0 && (g_gemm_variant == K_AUTO || a_xform)) {
-    // skinny GEMM (decode steps, single-row head GEMMs): a weight stream, HBM-bound
-    hipStream_t s = (hipStream_t)stream;
-    llmseg_prof_begin(s);
-    llmseg_prof_tag(p.M, p.N, p.K, 3000 + (p.res ? 20 : 0) + p.act * 2 + (a->out_f32 ? 1 : 0));
-    static const int sk_env = getenv("LLMSEG_SKINNY_SK") ? atoi(getenv("LLMSEG_SKINNY_SK")) : 1;
-    const bool sk = sk_env == 2 ? p.K >= 2048 : (sk_env && p.N <= 8192 && p.K >= 2048);      // fewer than 2 waves per SIMD otherwise: the workgroup's waves split K instead
-    const dim3 grid((unsigned)(sk ? (p.N + 3) / 4 : (p.N + 15) / 16));
-    const int of = a->out_f32 ? 1 : 0;
-#define LL_SKINNY_(AT, SKV)                                                                                   \
-    do {                                                                                                      \
-      if (p.M == 1) LL_LAUNCH_KERNEL((gemm_skinny_kernel<1, AT, SKV>), grid, dim3(256), 0, s, p, of);      \
-      else if (p.M == 2) LL_LAUNCH_KERNEL((gemm_skinny_kernel<2, AT, SKV>), grid, dim3(256), 0, s, p, of); \
-      else if (p.M <= 4) LL_LAUNCH_KERNEL((gemm_skinny_kernel<4, AT, SKV>), grid, dim3(256), 0, s, p, of); \
-      else LL_LAUNCH_KERNEL((gemm_skinny_kernel<8, AT, SKV>), grid, dim3(256), 0, s, p, of);               \
-    } while (0)
-#define LL_SKINNY(AT) do { if (sk) LL_SKINNY_(AT, true); else LL_SKINNY_(AT, false); } while (0)
-    if (p.a_norm_w) LL_SKINNY(1); else if (p.a_swiglu) LL_SKINNY(2); else LL_SKINNY(0);
-#undef LL_SKINNY_
-#undef LL_SKINNY
-    llmseg_prof_end(s, 2.0 * (double)a->M * (double)a->N * (double)a->K);
-    LL_LAUNCH_CHECK("gemm_skinny");
-    return LLMSEG_OK;
-  }
-  // ---- the launch
-  const bool pp = is_pp(kernel);
-  const int bm = pp ? pp_rows(kernel) : 128, bn = pp ? 256 : BN;
-  p.tiles_m = (p.M + bm - 1) / bm; p.tiles_n = (p.N + bn - 1) / bn;
-  // ping-pong tile walk (tools/gemm_bench.py sweeps): short matrices (Llama, <= 32 row tiles) with few column tiles (N = 4096: o, down,
-  // the dX products) keep all of M in one group so a W column tile is fetched once per XCD; with many column tiles (qkv, gate|up, lm_head at
-  // 16-24 images: 20-30 row tiles x 48-126 column tiles) an XCD's 32 concurrent tiles would be ONE column tile deep and re-stream all of A
-  // (63 MB at 24 images) per column tile -- 8 row tiles per group make the concurrent set 8 x 4 (+5..8 %: qkv 1017 -> 1100, gate|up
-  // 1215 -> 1300, lm_head 1234 -> 1310 TF/s at 16 images); tall ones (SAM, 384+ row tiles) walk 4 row tiles per group (+3..6 % at K = 5120)
-  p.group_m = group_m_env > 0 ? group_m_env : (p.tiles_m <= 32 ? ((p.tiles_n > 16 && p.tiles_m > 8) ? 8 : p.tiles_m) : 4);
-  hipStream_t s = (hipStream_t)stream;
-  llmseg_prof_begin(s);
-  llmseg_prof_tag(p.M, p.N, p.K, (kernel == K_PP128 ? 7 : kernel == K_T160 ? 6 : (int)kernel) * 1000 + (ta ? 200 : 0) + (tw ? 100 : 0) + (p.res ? 20 : 0) + p.act * 2 + (a->out_f32 ? 1 : 0) + 40 * (batch > 1) +
-                  10000 * (split > 1 ? split : 0));
-  const bool f = a->out_f32 != 0;
-  // Register-staging kernel (transposed operands / K % 64 != 0) on a grid that leaves most CUs idle with a long serial K loop (a lone
-  // workgroup takes 1.2-3 us per K-tile, all of it exposed latency: 512 x 256 x 2048 with W stored [K][N] was 75 us on 8 workgroups):
-  // K-slices as the (inner) batch index, fp32 slabs in the caller's workspace, epilogue in the reduce launch.
-  if (kernel == K_REG && batch2 == 1 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && a->workspace != nullptr && (((uintptr_t)a->workspace) & 15) == 0 &&
-      (!p.res || ((p.ldr & 3) == 0 && batch == 1)) && ((p.sC & 3) == 0 || batch == 1) && g_gemm_rsplit) {
-    const long tiles = (long)p.tiles_m * p.tiles_n * batch;
-    const int ntr = (p.K + BK - 1) / BK;
-    int S = (tiles * 4 <= ncu && ntr >= 8) ? (int)std::min<long>({(long)ncu / std::max<long>(tiles, 1), (long)ntr / 2, 32L}) : 1;
-    while (S > 1 && (double)S * batch * p.M * p.N * 4.0 > (double)a->workspace_bytes) --S;
-    if (S > 1) {
-      const int q = (ntr + S - 1) / S;
-      S = (ntr + q - 1) / q;
-    }
-    if (S > 1) {
-      const int q = (ntr + S - 1) / S;
-      GemmP ps = p;
-      ps.K = q * BK; ps.k_split_total = p.K; ps.batch1 = S;
-      ps.sA = ta ? (long)q * BK * p.lda : (long)q * BK; ps.sW = tw ? (long)q * BK * p.ldw : (long)q * BK;
-      ps.sA2 = p.sA; ps.sW2 = p.sW;                                   // the call's own batch index moves to the outer slot
-      ps.C = a->workspace; ps.ldc = p.N; ps.sC = (long)p.M * p.N; ps.sC2 = (long)S * p.M * p.N;
-      ps.bias = ps.gamma = ps.res = nullptr; ps.ldr = 0; ps.alpha = 1.f; ps.act = LLMSEG_ACT_NONE; ps.accum = 0;
-      ps.c_vec = 1; ps.r_vec = 0; ps.b_vec = 1;
-      const dim3 grid(p.tiles_m * p.tiles_n, (unsigned)(S * batch));
-      const int key = (ta ? 2 : 0) | (tw ? 1 : 0);
-      switch (key) {
-        case 0: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, false>), grid, dim3(NT), 0, s, ps); break;
-        case 1: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, true>), grid, dim3(NT), 0, s, ps); break;
-        case 2: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, false>), grid, dim3(NT), 0, s, ps); break;
-        default: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, true>), grid, dim3(NT), 0, s, ps); break;
-      }
-      const long total4 = (long)p.M * (p.N >> 2);
-      const unsigned rg = (unsigned)std::min<long>((total4 + 255) / 256, 4096);
-      LL_LAUNCH_KERNEL(splitk_reduce_kernel, dim3(rg, (unsigned)batch), dim3(256), 0, s, p, (const float*)a->workspace, S, f ? 1 : 0);
-      llmseg_prof_end(s, 2.0 * (double)a->M * (double)a->N * (double)a->K * (double)batch);
-      LL_LAUNCH_CHECK("gemm_bf16_tn (K-sliced)");
-      return LLMSEG_OK;
-    }
-  }
-  if (pp && split > 1) {
-    // K-slices as the batch dimension of the ping-pong kernel: slice s reads A / W columns [s q 64, ...), writes fp32 slab s
-    GemmP ps = p;
-    const int q = (nt + split - 1) / split;
-    ps.K = q * BK; ps.kt_total = nt; ps.batch1 = split;
-    ps.sA = ps.sW = (long)q * BK; ps.sA2 = ps.sW2 = ps.sC2 = 0;
-    ps.C = a->workspace; ps.ldc = p.N; ps.sC = (long)p.M * p.N;
-    ps.bias = ps.gamma = ps.res = nullptr; ps.ldr = 0; ps.alpha = 1.f; ps.act = LLMSEG_ACT_NONE; ps.accum = 0;
-    ps.c_vec = 1; ps.r_vec = 0; ps.b_vec = 1; ps.A2 = ps.W2 = nullptr;
-    dim3 grid(p.tiles_m * p.tiles_n, (unsigned)split);
-    if (kernel == K_T160) LL_LAUNCH_KERNEL(gemm_bf16_tn_t160_kernel, grid, dim3(NTB), 0, s, ps);
-    else launch_pp<true, false>(kernel, ps, grid, s);
-    // the reduce launch: sums the slabs (+ the extension product's) and applies the epilogue; the caller's tail rides in it where a row kernel can do both
-    const float* slabs = (const float*)a->workspace;
-    const int S2 = split + (p.A2 ? 1 : 0);
-    const int cpt = ((p.N >> 3) + 255) / 256;                 // 8-column chunks per thread of the workgroup-per-row kernels
-    const llmseg_gemm_args* r = tail ? tail->req : nullptr;
-    // the row kernel only where llmseg_norm would run its workgroup-per-row kernel on this shape (same arithmetic, same bits) and the epilogue is the plain residual add
-    static const long wg_max_rows = getenv("LLMSEG_NORM_WG_MAX") ? atol(getenv("LLMSEG_NORM_WG_MAX")) : 2048;
-    const bool fuse_norm = tail && tail->kind == TAIL_NORM && !f && p.alpha == 1.f && !p.bias && !p.gamma && p.act == LLMSEG_ACT_NONE && p.M >= 64 && p.M < wg_max_rows &&
-                           p.N >= 2048 && p.N <= 8192 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.res || (p.ldr & 7) == 0) && (r->ldn & 7) == 0 &&
-                           ((((uintptr_t)p.C) | ((uintptr_t)p.res) | ((uintptr_t)r->norm_w) | ((uintptr_t)r->norm_out)) & 15) == 0;
-    const bool fuse_nb = tail && tail->kind == TAIL_NB && !f && p.alpha == 1.f && !p.bias && !p.gamma && !p.res && p.act == LLMSEG_ACT_NONE && p.M >= 64 && p.N >= 2048 &&
-                         p.N <= 8192 && (p.N & 7) == 0;       // == where llmseg_norm_bwd_add runs its workgroup-per-row kernel (same arithmetic, same bits)
-    const bool fuse_dl = tail && tail->kind == TAIL_DL && !f && !p.bias && !p.gamma && !p.res && p.act == LLMSEG_ACT_NONE && p.N <= 8192 && (p.N & 127) == 0 && (p.ldc & 7) == 0;
-    if (fuse_dl) {
-#define LL_RDL(C) LL_LAUNCH_KERNEL(splitk_reduce_delta_kernel<C>, dim3((unsigned)p.M), dim3(256), 0, s, p, slabs, S2, (const bf16_t*)r->dl_o, (long)r->dl_ldo, r->dl_out, \
-                                   (int)r->dl_heads, (int)r->dl_T)
-      if (cpt <= 1) LL_RDL(1); else if (cpt <= 2) LL_RDL(2); else LL_RDL(4);
-#undef LL_RDL
-    } else if (fuse_nb) {
-      const int rc = llmseg_reduce_lora_normbwd(slabs, S2, p.M, p.N, r->nb_x, r->nb_w, r->C, r->nb_eps, r->nb_rms, r->nb_dres, (void*)r->nb_lora_t, r->nb_lora_ldt, r->nb_lora_w0,
-                                                r->nb_lora_w1, r->nb_lora_alpha, (const llmseg_dropout*)r->nb_lora_drop, r->nb_lora_part, r->nb_lora_S, r->nb_lora_scale,
-                                                r->nb_lora_zero, stream);
-      if (rc != LLMSEG_OK) return rc;
-    } else if (fuse_norm) {
-#define LL_RNORM(C) LL_LAUNCH_KERNEL(splitk_reduce_rmsnorm_kernel<C>, dim3((unsigned)p.M), dim3(256), 0, s, p, slabs, S2, (const bf16_t*)r->norm_w, r->norm_eps, \
-                                     (bf16_t*)r->norm_out, (long)r->ldn)
-      if (cpt <= 1) LL_RNORM(1); else if (cpt <= 2) LL_RNORM(2); else LL_RNORM(4);
-#undef LL_RNORM
-    } else {
-      const long total4 = (long)p.M * (p.N >> 2);
-      const unsigned rg = (unsigned)std::min<long>((total4 + 255) / 256, 4096);
-      LL_LAUNCH_KERNEL(splitk_reduce_kernel, dim3(rg), dim3(256), 0, s, p, slabs, S2, f ? 1 : 0);
-    }
-    if (fuse_dl || fuse_nb || fuse_norm) tail->done = true;
-  } else if (pp) {
-    // one K-slice of a ping-pong tile (K_T160 never gets here: every plan of it has slices).  Fused Llama-layer epilogues (llmseg_gemm_args.fx) on shapes whose
-    // tiles hold whole pairs; gemm_fx runs the pointwise launch otherwise.  The 128-row tile serves the layer at 2 images per micro-step, the 256-row tile the fused
-    // accumulation window and 24-image micro-batches.
-    dim3 grid(p.tiles_m * p.tiles_n, (unsigned)batch);
-    const bool fx_ok = tail && tail->kind == TAIL_FX && !f && batch == 1 &&
-                       (a->fx == LLMSEG_FX_ROPE ? (p.N % 256) == 0 && p.A2 != nullptr
-                        : a->fx == LLMSEG_FX_SWIGLU ? (p.fx_I % 128) == 0 : (p.N % 64) == 0);
-    if (fx_ok) {
-      GemmP q = p;
-      q.fx = a->fx;
-      if (a->fx == LLMSEG_FX_SWIGLU_BWD) q.C = (bf16_t*)a->C - a->N;      // gemm_fx pointed C at the up half for the two-launch route: back to the row start
-      if (a->fx == LLMSEG_FX_ROPE) launch_pp<false, true, FX_ROPE>(kernel, q, grid, s);
-      else if (a->fx == LLMSEG_FX_SWIGLU) launch_pp<false, false, FX_SWIGLU>(kernel, q, grid, s);
-      else launch_pp<false, false, FX_SWIGLU_BWD>(kernel, q, grid, s);
-      tail->done = true;
-    } else if (p.A2) launch_pp<false, true>(kernel, p, grid, s);      // bf16 out only (checked above)
-    else if (f) launch_pp<true, false>(kernel, p, grid, s);
-    else launch_pp<false, false>(kernel, p, grid, s);
-  } else {
-    dim3 grid(p.tiles_m * p.tiles_n, (unsigned)batch);
-    if (kernel == K_GLDS) {
-      if (f) LL_LAUNCH_KERNEL((gemm_bf16_tn_glds_kernel<true>), grid, dim3(NT), 0, s, p);
-      else LL_LAUNCH_KERNEL((gemm_bf16_tn_glds_kernel<false>), grid, dim3(NT), 0, s, p);
-    } else {
-      const int key = (f ? 4 : 0) | (ta ? 2 : 0) | (tw ? 1 : 0);
-      switch (key) {
-        case 0: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, false, false>), grid, dim3(NT), 0, s, p); break;
-        case 1: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, false, true>), grid, dim3(NT), 0, s, p); break;
-        case 2: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, true, false>), grid, dim3(NT), 0, s, p); break;
-        case 3: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<false, true, true>), grid, dim3(NT), 0, s, p); break;
-        case 4: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, false>), grid, dim3(NT), 0, s, p); break;
-        case 5: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, false, true>), grid, dim3(NT), 0, s, p); break;
-        case 6: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, false>), grid, dim3(NT), 0, s, p); break;
-        default: LL_LAUNCH_KERNEL((gemm_bf16_tn_kernel<true, true, true>), grid, dim3(NT), 0, s, p); break;
-      }
-    }
-  }
-  llmseg_prof_end(s, 2.0 * (double)a->M * (double)a->N * (double)a->K * (double)batch);
-  LL_LAUNCH_CHECK("gemm_bf16_tn");
-  return LLMSEG_OK;
 }
