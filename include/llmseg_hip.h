@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 11
+#define LLMSEG_ABI_VERSION 12
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -431,6 +431,29 @@ int llmseg_mask_targets(const uint8_t* segs, const uint8_t* gt, const int32_t* g
                         int32_t Wg, int64_t* counts, int64_t* gt_area, double* iou, double* iop, void* stream);
 int llmseg_resize_aa(const uint8_t* segs, void* out, int32_t K, int32_t H, int32_t W, int32_t out_size, const int32_t* y0, const int32_t* ny,
                      const double* wy, const int32_t* x0, const int32_t* nx, const double* wx, int32_t taps, void* stream);
+
+/* ---- the COCO RLE codec on the device: the FILE format of the proposals (prepare_datasets: pycocotools `mask.encode`; loader: rleFrString) --
+ * rle_encode: dense masks uint8 [K][H][W] (row-major, non-zero = inside; 0 / 255 masks count like 0 / 1) -> maskApi rleEncode + rleToString.
+ *   Runs walk the image column-major (p = x H + y), alternate 0 / 1 starting with a zero run (the first count is 0 when pixel (0, 0) is set) and
+ *   continue across column boundaries; counts from the fourth on are stored as deltas against the count two back; characters are 5-bit groups,
+ *   low group first, bit 5 = continuation, bit 4 of the last group = sign, + 48.  H W < 2^31.
+ *   counts uint32 [K][cap_counts], chars uint8 [K][cap_chars]; n_counts[k] / n_chars[k] int32 ALWAYS hold the true sizes.  A mask that exceeds a
+ *   cap has its row truncated -- counts: the first cap_counts run lengths; chars: the first cap_chars characters of the counts that were
+ *   stored -- and nothing is written past either row; the caller retries with caps >= max(n_counts), max(n_chars) (a count needs at most 7
+ *   characters).  Output positions come from prefix sums (no atomics on any output): the same input gives the same bytes on every run.
+ *   workspace >= llmseg_rle_encode_ws_bytes(K, H, W) bytes, 16-byte aligned.
+ * rle_parse: the K compressed strings, concatenated (chars [total], char_offsets int64 [K+1] on the device, char_offsets[0] = 0, total =
+ *   char_offsets[K]) -> the inputs of llmseg_rle_decode: run_ends uint32 = inclusive prefix sums (mod 2^32) of each mask's counts, concatenated;
+ *   run_offsets int64 [K+1] delimits the slices.  A string never has more counts than characters: run_ends needs room for `total` elements.
+ *   Strings of at most 7 groups per count (every encoder's output for H W < 2^31) give the bits of the host parse; any other byte content gives
+ *   unspecified VALUES, but no read leaves chars [0, total) and no write leaves run_ends [0, total) / run_offsets [0, K + 1).
+ *   workspace >= llmseg_rle_parse_ws_bytes(K, total) bytes. */
+int64_t llmseg_rle_encode_ws_bytes(int32_t K, int32_t H, int32_t W);
+int llmseg_rle_encode(const uint8_t* masks, int32_t K, int32_t H, int32_t W, uint32_t* counts, int32_t* n_counts, int32_t cap_counts, uint8_t* chars,
+                      int32_t* n_chars, int32_t cap_chars, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t llmseg_rle_parse_ws_bytes(int32_t K, int64_t total_chars);
+int llmseg_rle_parse(const uint8_t* chars, const int64_t* char_offsets, int32_t K, uint32_t* run_ends, int64_t* run_offsets, void* workspace,
+                     int64_t workspace_bytes, void* stream);
 
 /* ---- backward pass + optimizer (trainable part: LoRA'd Llama stack, embed/lm_head, text_hidden_fcs, mask-selection head) -----
  * GEMM-shaped gradients use llmseg_gemm_bf16 with trans_a / trans_w (dX = dY W, dW = dY^T X); the kernels below are the

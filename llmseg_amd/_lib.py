@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 11         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 12         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
 NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
@@ -127,6 +127,10 @@ SIGNATURES = {
     "llmseg_intersection_union": [_p, _p, _i64, _i32, _p, _p],
     "llmseg_union_resize_iou": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
     "llmseg_rle_decode": [_p, _p, _p, _i32, _i32, _i32, _i32, _p],
+    "llmseg_rle_encode_ws_bytes": [_i32, _i32, _i32],
+    "llmseg_rle_encode": [_p, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _i32, _p, _i64, _p],
+    "llmseg_rle_parse_ws_bytes": [_i32, _i64],
+    "llmseg_rle_parse": [_p, _p, _i32, _p, _p, _p, _i64, _p],
     "llmseg_mask_targets": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p],
     "llmseg_gt_resample": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
     "llmseg_proposal_targets": [_p, _p, _p, _i32, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p],
@@ -177,7 +181,8 @@ def load():
         fn.argtypes = argtypes
         fn.restype = (C.c_char_p if name in ("llmseg_last_error", "llmseg_prof_dominant_kernel") else
                       C.c_double if name == "llmseg_prof_dominant_bytes" else C.c_int64 if name in ("llmseg_struct_size", "llmseg_launch_count", "llmseg_image_resize_workspace", "llmseg_mask_small_regions_workspace",
-                                                                                            "llmseg_image_resize_filter_workspace", "llmseg_clip_preprocess_workspace") else C.c_int)
+                                                                                            "llmseg_image_resize_filter_workspace", "llmseg_clip_preprocess_workspace",
+                                                                                            "llmseg_rle_encode_ws_bytes", "llmseg_rle_parse_ws_bytes") else C.c_int)
     # ABI guard at load time: this binding's structs must be the library's (the entry points check `struct_size` per call as well)
     if lib.llmseg_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI version {lib.llmseg_version()} != {ABI_VERSION} of this binding (rebuild: llmseg_amd/csrc/build.sh)")

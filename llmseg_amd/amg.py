@@ -210,15 +210,22 @@ def to_records(out, original_size, output_mode="coco_rle"):
     reference's preparation scripts store (prepare_datasets/prepare_ReasonSeg.py:90-97) or the binary mask."""
     from .targets import rle_encode_masks
     H, W = int(original_size[0]), int(original_size[1])
-    masks = out["masks"].cpu()
-    boxes = out["boxes"].cpu().tolist()
-    seg = rle_encode_masks(masks) if output_mode == "coco_rle" else [m.numpy().astype(bool) for m in masks]
+    masks = out["masks"]
+    K = int(masks.shape[0])
+    if output_mode == "coco_rle":                        # device masks are encoded on the device: only the strings cross to the host
+        seg = rle_encode_masks(masks)
+    else:
+        seg = [m.numpy().astype(bool) for m in masks.cpu()]
+    boxes = out["boxes"].cpu().tolist()                  # one copy per field, not one read per record
+    areas, ious, stabs = (out[n].cpu().tolist() for n in ("areas", "iou_preds", "stability_score"))
+    points = out["points"].cpu().tolist()
+    crops = out["crop_boxes"].cpu().tolist() if "crop_boxes" in out else None
     recs = []
-    for k in range(masks.shape[0]):
+    for k in range(K):
         x0, y0, x1, y1 = boxes[k]
-        recs.append({"segmentation": seg[k], "area": int(out["areas"][k]), "bbox": [x0, y0, x1 - x0, y1 - y0],
-                     "predicted_iou": float(out["iou_preds"][k]), "point_coords": [out["points"][k].tolist()],
-                     "stability_score": float(out["stability_score"][k]),
-                     "crop_box": [0, 0, W, H] if "crop_boxes" not in out else
-                     [int(out["crop_boxes"][k][0]), int(out["crop_boxes"][k][1]), int(out["crop_boxes"][k][2] - out["crop_boxes"][k][0]), int(out["crop_boxes"][k][3] - out["crop_boxes"][k][1])]})
+        recs.append({"segmentation": seg[k], "area": int(areas[k]), "bbox": [x0, y0, x1 - x0, y1 - y0],
+                     "predicted_iou": float(ious[k]), "point_coords": [points[k]],
+                     "stability_score": float(stabs[k]),
+                     "crop_box": [0, 0, W, H] if crops is None else
+                     [int(crops[k][0]), int(crops[k][1]), int(crops[k][2] - crops[k][0]), int(crops[k][3] - crops[k][1])]})
     return recs

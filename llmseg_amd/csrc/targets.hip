@@ -256,6 +256,242 @@ __global__ __launch_bounds__(256) void proposal_targets_kernel(const uint8_t* __
   }
 }
 
+// ---- COCO RLE codec (the proposals' FILE format: pycocotools rleEncode + rleToString / rleFrString) ---------------------------------------
+// Encode.  The mask is row-major but the runs walk it column-major (p = x H + y).  A UNIT is RE_SEG rows of one column; units are ordered as
+// the walk meets them (u = x S + s, S = ceil(H / RE_SEG)).  A lane owns four adjacent columns of one row segment and loops over y: the wave
+// reads 256 contiguous bytes per row, no transpose, and a tall image spreads over S lanes per column.  A TRANSITION is a pixel that differs
+// from its predecessor in the walk (pixel 0 against a virtual 0); t_0 < t_1 < ... are their positions.  counts[i] = t_i - t_(i-1) (t_-1 = 0),
+// the last count is H W - t_(n-1).  Three steps, every output position from a prefix sum:
+//   walk<false>: per unit {number of transitions, positions of its last three}                                   -> rec[k][u]
+//   scan       : per mask, exclusive scan over the units of {sum, last three transitions of the concatenation}     -> rec[k][u], n_counts
+//   walk<true> : the same walk with the unit's carry {index of its first transition, t_(i-1), t_(i-2), t_(i-3)}: writes counts[i] (i < cap)
+//                and the unit's character total (the delta needs three transitions back)                          -> rec[k][u].x
+//   chars      : per mask, deltas of the stored counts -> character lengths -> scan -> characters; n_chars = sum of the units' totals
+constexpr int RE_SEG = 64;
+constexpr uint32_t RE_NONE = 0xffffffffu;                 // no transition (positions are < 2^31)
+struct RleAgg { uint32_t n, a1, a2, a3; };                // a1 = the most recent transition
+__device__ __forceinline__ RleAgg rle_join(const RleAgg& l, const RleAgg& r) {      // l earlier in the walk; associative
+  RleAgg o;
+  o.n = l.n + r.n;
+  if (r.a1 == RE_NONE) { o.a1 = l.a1; o.a2 = l.a2; o.a3 = l.a3; }
+  else if (r.a2 == RE_NONE) { o.a1 = r.a1; o.a2 = l.a1; o.a3 = l.a2; }
+  else if (r.a3 == RE_NONE) { o.a1 = r.a1; o.a2 = r.a2; o.a3 = l.a1; }
+  else { o.a1 = r.a1; o.a2 = r.a2; o.a3 = r.a3; }
+  return o;
+}
+__device__ __forceinline__ RleAgg rle_shfl_up(const RleAgg& v, int o) {
+  RleAgg r;
+  r.n = __shfl_up(v.n, o, 64); r.a1 = __shfl_up(v.a1, o, 64); r.a2 = __shfl_up(v.a2, o, 64); r.a3 = __shfl_up(v.a3, o, 64);
+  return r;
+}
+// characters of one (delta-coded) count: 5-bit groups until the rest is pure sign extension
+__device__ __forceinline__ int rle_nchars(long x) {
+  int n = 0;
+  bool more;
+  do { const int c = (int)(x & 0x1f); x >>= 5; more = (c & 0x10) ? x != -1 : x != 0; ++n; } while (more);
+  return n;
+}
+// inclusive scan over the 256 threads of a workgroup (wave64 shuffles, then the four wave totals through LDS); total = the workgroup's sum
+template <typename T>
+__device__ __forceinline__ T block_scan256(T v, T* wt, T& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const T t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+  __syncthreads();                                         // the previous scan's readers are done with wt
+  if (lane == 63) wt[wave] = inc;
+  __syncthreads();
+  T pre = 0;
+  for (int w = 0; w < wave; ++w) pre += wt[w];
+  total = wt[0] + wt[1] + wt[2] + wt[3];
+  return inc + pre;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void rle_walk_kernel(const uint8_t* __restrict__ masks, int H, int W, int S, int WQ, int bpm, uint4* __restrict__ rec,
+                                                      uint32_t* __restrict__ counts, int cap_counts) {
+  const int k = blockIdx.x / bpm;
+  const long g = (long)(blockIdx.x - k * bpm) * 256 + threadIdx.x;
+  if (g >= (long)S * WQ) return;
+  const int s = (int)(g / WQ), x4 = (int)(g % WQ) * 4;
+  const uint8_t* m = masks + (long)k * H * W;
+  const int y0 = s * RE_SEG, y1 = min(H, y0 + RE_SEG), nc = min(4, W - x4);
+  const bool vec = (W & 3) == 0 && (((uintptr_t)masks) & 3) == 0;
+  const uint32_t valid = nc == 4 ? 0x01010101u : (0x01010101u & ((1u << (8 * nc)) - 1u));
+  auto load4 = [&](int y) -> uint32_t {                    // byte c = 1 where pixel (y, x4 + c) is set
+    uint32_t w = 0;
+    if (vec) w = *reinterpret_cast<const uint32_t*>(m + (long)y * W + x4);
+    else
+      for (int c = 0; c < nc; ++c) w |= (uint32_t)m[(long)y * W + x4 + c] << (8 * c);
+    w = (w | (w >> 4)) & 0x0f0f0f0fu; w = (w | (w >> 2)) & 0x03030303u;
+    return (w | (w >> 1)) & 0x01010101u;
+  };
+  uint32_t prev;                                           // the walk's predecessors of row y0: the row above, or the foot of the column to the left
+  if (y0 > 0) prev = load4(y0 - 1);
+  else prev = ((load4(H - 1) << 8) | (x4 > 0 ? (uint32_t)(m[(long)(H - 1) * W + x4 - 1] != 0) : 0u)) & valid;
+  uint32_t n[4], a1[4], a2[4], a3[4], len[4];
+  uint4* R = rec + (long)k * W * S;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    n[c] = 0; a1[c] = a2[c] = a3[c] = RE_NONE; len[c] = 0;
+    if (WRITE && c < nc) { const uint4 r = R[(long)(x4 + c) * S + s]; n[c] = r.x; a1[c] = r.y; a2[c] = r.z; a3[c] = r.w; }      // n = index of the next transition
+  }
+  uint32_t* crow = WRITE ? counts + (long)k * cap_counts : nullptr;
+  auto emit = [&](uint32_t i, uint32_t p, uint32_t b1, uint32_t b2, uint32_t b3) -> uint32_t {      // count i ends at p; -> its characters
+    const uint32_t cnt = p - (i >= 1 ? b1 : 0u);
+    const long d = i >= 3 ? (long)cnt - (long)(b2 - b3) : (long)cnt;
+    if (i < (uint32_t)cap_counts) crow[i] = cnt;
+    return (uint32_t)rle_nchars(d);
+  };
+  for (int yb = y0; yb < y1; yb += 8) {
+    uint32_t v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = yb + j < y1 ? load4(yb + j) : 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (yb + j >= y1) break;
+      const uint32_t d = v[j] ^ prev;
+      prev = v[j];
+      if (!d) continue;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (!((d >> (8 * c)) & 1u)) continue;
+        const uint32_t p = (uint32_t)(x4 + c) * (uint32_t)H + (uint32_t)(yb + j);
+        if (WRITE) len[c] += emit(n[c], p, a1[c], a2[c], a3[c]);
+        ++n[c]; a3[c] = a2[c]; a2[c] = a1[c]; a1[c] = p;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (c >= nc) continue;
+    if (WRITE) {
+      if (x4 + c == W - 1 && s == S - 1) len[c] += emit(n[c], (uint32_t)H * (uint32_t)W, a1[c], a2[c], a3[c]);      // the run that reaches the end of the walk
+      R[(long)(x4 + c) * S + s].x = len[c];
+    } else R[(long)(x4 + c) * S + s] = make_uint4(n[c], a1[c], a2[c], a3[c]);
+  }
+}
+
+// rec[k][u] <- exclusive scan over u of rle_join; n_counts[k] = transitions + 1.  One workgroup per mask, four units per thread, carry across chunks.
+__global__ __launch_bounds__(256) void rle_scan_kernel(uint4* __restrict__ rec, int U, int32_t* __restrict__ n_counts) {
+  __shared__ RleAgg wt[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint4* R = rec + (long)blockIdx.x * U;
+  const RleAgg none = {0u, RE_NONE, RE_NONE, RE_NONE};
+  RleAgg carry = none;
+  for (int base = 0; base < U; base += 1024) {
+    const int u0 = base + (int)threadIdx.x * 4;
+    RleAgg e[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      e[j] = none;
+      if (u0 + j < U) { const uint4 r = R[u0 + j]; e[j] = RleAgg{r.x, r.y, r.z, r.w}; }
+    }
+    RleAgg inc = rle_join(rle_join(e[0], e[1]), rle_join(e[2], e[3]));
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const RleAgg t = rle_shfl_up(inc, o); if (lane >= o) inc = rle_join(t, inc); }
+    RleAgg pre = rle_shfl_up(inc, 1);                      // exclusive inside the wave
+    if (lane == 0) pre = none;
+    if (lane == 63) wt[wave] = inc;
+    __syncthreads();
+    RleAgg before = carry, total = carry;
+    for (int w = 0; w < 4; ++w) { if (w < wave) before = rle_join(before, wt[w]); total = rle_join(total, wt[w]); }
+    pre = rle_join(before, pre);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (u0 + j < U) { R[u0 + j] = make_uint4(pre.n, pre.a1, pre.a2, pre.a3); pre = rle_join(pre, e[j]); }
+    carry = total;
+    __syncthreads();                                       // wt is rewritten by the next chunk
+  }
+  if (threadIdx.x == 0) n_counts[blockIdx.x] = (int32_t)(carry.n + 1u);
+}
+
+// stored counts -> deltas -> characters at scanned offsets; n_chars[k] = the units' character totals (true also when a cap cut the rows)
+__global__ __launch_bounds__(256) void rle_chars_kernel(const uint4* __restrict__ rec, int U, const uint32_t* __restrict__ counts, const int32_t* __restrict__ n_counts,
+                                                       int cap_counts, uint8_t* __restrict__ chars, int32_t* __restrict__ n_chars, int cap_chars) {
+  __shared__ uint32_t wt[4];
+  const int k = blockIdx.x;
+  const uint32_t* c = counts + (long)k * cap_counts;
+  uint8_t* out = chars + (long)k * cap_chars;
+  const int n = min(n_counts[k], cap_counts);
+  uint32_t carry = 0, total;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    long d = 0;
+    uint32_t len = 0;
+    if (i < n) { d = (long)c[i]; if (i >= 3) d -= (long)c[i - 2]; len = (uint32_t)rle_nchars(d); }
+    uint32_t pos = carry + block_scan256(len, wt, total) - len;
+    for (uint32_t j = 0; j < len; ++j, ++pos) {
+      int ch = (int)(d & 0x1f);
+      d >>= 5;
+      if (j + 1 < len) ch |= 0x20;
+      if (pos < (uint32_t)cap_chars) out[pos] = (uint8_t)(ch + 48);
+    }
+    carry += total;
+  }
+  uint32_t sum = 0;
+  for (int u = threadIdx.x; u < U; u += 256) sum += rec[(long)k * U + u].x;
+  block_scan256(sum, wt, total);
+  if (threadIdx.x == 0) n_chars[k] = (int32_t)total;
+}
+
+// Parse.  Every count ends at a character without the continuation bit (bit 5), so the number of such characters before character j is the
+// index of j's count, inside the mask and -- strings end on one -- in the concatenated output.  One workgroup per mask walks its string in
+// chunks of 256 characters; the thread at a count's LAST character gathers the count's (at most 7) groups, and the delta coding
+// cnt[i] = v[i] + cnt[i - 2] (i >= 3) is two interleaved prefix sums (odd indices from 1, even indices from 2; index 0 stands alone), followed
+// by the inclusive sum to run ends: block scans with a carry across the chunks, all mod 2^32.
+__global__ __launch_bounds__(256) void rle_parse_count_kernel(const uint8_t* __restrict__ chars, const int64_t* __restrict__ co, int32_t* __restrict__ n) {
+  __shared__ uint32_t wt[4];
+  const long a = co[blockIdx.x], b = co[blockIdx.x + 1];
+  uint32_t c = 0, total;
+  for (long j = a + threadIdx.x; j < b; j += 256) c += (((int)chars[j] - 48) & 0x20) == 0;
+  block_scan256(c, wt, total);
+  if (threadIdx.x == 0) n[blockIdx.x] = (int32_t)total;
+}
+__global__ __launch_bounds__(256) void rle_parse_offsets_kernel(const int32_t* __restrict__ n, int K, int64_t* __restrict__ ro) {
+  __shared__ long wt[4];
+  long carry = 0, total;
+  if (threadIdx.x == 0) ro[0] = 0;
+  for (int base = 0; base < K; base += 256) {
+    const int k = base + (int)threadIdx.x;
+    const long inc = block_scan256<long>(k < K ? (long)n[k] : 0L, wt, total);
+    if (k < K) ro[k + 1] = carry + inc;
+    carry += total;
+  }
+}
+__global__ __launch_bounds__(256) void rle_parse_kernel(const uint8_t* __restrict__ chars, const int64_t* __restrict__ co, const int64_t* __restrict__ ro,
+                                                       uint32_t* __restrict__ run_ends) {
+  __shared__ uint32_t wt[4];
+  const long a = co[blockIdx.x], b = co[blockIdx.x + 1];
+  uint32_t* out = run_ends + ro[blockIdx.x];
+  uint32_t c_idx = 0, c_odd = 0, c_even = 0, c_end = 0, total;
+  for (long base = a; base < b; base += 256) {
+    const long j = base + threadIdx.x;
+    const int bj = j < b ? (int)chars[j] - 48 : 0x20;
+    const bool last = j < b && (bj & 0x20) == 0;
+    const uint32_t i = c_idx + block_scan256<uint32_t>(last ? 1u : 0u, wt, total) - (last ? 1u : 0u);      // this count's index in its mask
+    c_idx += total;
+    uint32_t val = 0;
+    if (last) {
+      long st = j;                                         // first character of the count: at most 6 continuation characters back, inside the mask
+      while (st > a && j - st < 6 && ((((int)chars[st - 1] - 48) & 0x20) != 0)) --st;
+      unsigned long x = 0;
+      for (long q = st; q <= j; ++q) x |= (unsigned long)(((int)chars[q] - 48) & 0x1f) << (5 * (int)(q - st));
+      if (bj & 0x10) x |= ~0ul << (5 * (int)(j - st + 1));
+      val = (uint32_t)x;
+    }
+    const bool odd = (i & 1u) != 0;
+    const uint32_t s_odd = c_odd + block_scan256<uint32_t>(last && odd ? val : 0u, wt, total);
+    c_odd += total;
+    const uint32_t s_even = c_even + block_scan256<uint32_t>(last && !odd && i >= 2 ? val : 0u, wt, total);
+    c_even += total;
+    const uint32_t cnt = !last ? 0u : i == 0 ? val : odd ? s_odd : s_even;
+    const uint32_t end = c_end + block_scan256<uint32_t>(cnt, wt, total);
+    c_end += total;
+    if (last) out[i] = end;
+  }
+}
+
 }  // namespace
 
 extern "C" int llmseg_gt_resample(const uint8_t* gt, const int32_t* gy, const int32_t* gx, uint8_t* out, int32_t H, int32_t W, int32_t Hg, int32_t Wg, void* stream) {
@@ -298,6 +534,47 @@ extern "C" int llmseg_rle_decode(const uint32_t* run_ends, const int64_t* offset
   LL_LAUNCH_KERNEL(rle_decode_kernel, dim3((unsigned)((n + 255) / 256 > 65535 * 16 ? 65535 * 16 : (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, run_ends,
                      offsets, out, K, H, W, hwk);
   LL_LAUNCH_CHECK("rle_decode");
+  return LLMSEG_OK;
+}
+
+extern "C" int64_t llmseg_rle_encode_ws_bytes(int32_t K, int32_t H, int32_t W) {
+  if (K <= 0 || H <= 0 || W <= 0) return 0;
+  return (int64_t)K * W * ((H + RE_SEG - 1) / RE_SEG) * (int64_t)sizeof(uint4);      // one record per unit
+}
+
+extern "C" int llmseg_rle_encode(const uint8_t* masks, int32_t K, int32_t H, int32_t W, uint32_t* counts, int32_t* n_counts, int32_t cap_counts, uint8_t* chars,
+                                 int32_t* n_chars, int32_t cap_chars, void* workspace, int64_t workspace_bytes, void* stream) {
+  LL_CHECK(masks && counts && n_counts && chars && n_chars && K > 0 && H > 0 && W > 0 && cap_counts > 0 && cap_chars > 0, "rle_encode: bad arguments");
+  LL_CHECK((long)H * W < (1L << 31), "rle_encode: H * W must be below 2^31");
+  LL_CHECK(workspace && (((uintptr_t)workspace) & 15) == 0 && workspace_bytes >= llmseg_rle_encode_ws_bytes(K, H, W),
+           "rle_encode: workspace of llmseg_rle_encode_ws_bytes(K, H, W) bytes, 16-byte aligned");
+  const int S = (H + RE_SEG - 1) / RE_SEG, WQ = (W + 3) / 4;
+  const long bpm = ((long)S * WQ + 255) / 256, U = (long)W * S;
+  LL_CHECK(bpm * K < (1L << 24) && U < (1L << 31), "rle_encode: too many masks for one launch at this size");
+  uint4* rec = (uint4*)workspace;
+  LL_LAUNCH_KERNEL(rle_walk_kernel<false>, dim3((unsigned)(bpm * K)), dim3(256), 0, (hipStream_t)stream, masks, H, W, S, WQ, (int)bpm, rec, (uint32_t*)nullptr, 0);
+  LL_LAUNCH_KERNEL(rle_scan_kernel, dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream, rec, (int)U, n_counts);
+  LL_LAUNCH_KERNEL(rle_walk_kernel<true>, dim3((unsigned)(bpm * K)), dim3(256), 0, (hipStream_t)stream, masks, H, W, S, WQ, (int)bpm, rec, counts, cap_counts);
+  LL_LAUNCH_KERNEL(rle_chars_kernel, dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream, (const uint4*)rec, (int)U, (const uint32_t*)counts, (const int32_t*)n_counts,
+                   cap_counts, chars, n_chars, cap_chars);
+  LL_LAUNCH_CHECK("rle_encode");
+  return LLMSEG_OK;
+}
+
+extern "C" int64_t llmseg_rle_parse_ws_bytes(int32_t K, int64_t total_chars) {
+  if (K <= 0 || total_chars < 0) return 0;
+  return ((int64_t)K * (int64_t)sizeof(int32_t) + 255) / 256 * 256;      // counts per mask
+}
+
+extern "C" int llmseg_rle_parse(const uint8_t* chars, const int64_t* char_offsets, int32_t K, uint32_t* run_ends, int64_t* run_offsets, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  LL_CHECK(chars && char_offsets && run_ends && run_offsets && K > 0, "rle_parse: bad arguments");
+  LL_CHECK(workspace && (((uintptr_t)workspace) & 3) == 0 && workspace_bytes >= llmseg_rle_parse_ws_bytes(K, 0), "rle_parse: workspace of llmseg_rle_parse_ws_bytes(K, total) bytes");
+  int32_t* n = (int32_t*)workspace;
+  LL_LAUNCH_KERNEL(rle_parse_count_kernel, dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream, chars, char_offsets, n);
+  LL_LAUNCH_KERNEL(rle_parse_offsets_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int32_t*)n, K, run_offsets);
+  LL_LAUNCH_KERNEL(rle_parse_kernel, dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream, chars, char_offsets, (const int64_t*)run_offsets, run_ends);
+  LL_LAUNCH_CHECK("rle_parse");
   return LLMSEG_OK;
 }
 

@@ -7,9 +7,12 @@ Mirrors, with the same names and argument meaning where they exist in the refere
     `skimage.transform.resize(order=0)`, then |seg & gt| / |seg | gt| and |seg & gt| / |seg|;
   * the dataset's proposal maps (utils/reason_seg_dataset.py:166-173): float64 zero-padded square -> `F.interpolate(size=(256, 256),
     mode="bilinear", align_corners=False, antialias=True)` -> bf16.
-Host side: parsing the COCO run-length strings and building the (tiny) index / tap tables in float64; every per-pixel operation runs in
-libllmseg_hip.so (`llmseg_rle_decode`, `llmseg_mask_targets`, `llmseg_resize_aa`)."""
+Host side: building the (tiny) index / tap tables in float64; every per-pixel operation runs in libllmseg_hip.so (`llmseg_rle_decode`,
+`llmseg_mask_targets`, `llmseg_resize_aa`).  The COCO run-length FILE format is a device codec too: `rle_encode_masks` of device masks is
+`llmseg_rle_encode` (only the characters cross to the host), `decode_rles` of compressed strings is `llmseg_rle_parse` + `llmseg_rle_decode`
+(the host joins the bytes); `SamMaskReader` is the reference's reader class over a `masks.json` (`llmseg_amd.prepare` writes one)."""
 import ctypes as C
+import json
 
 import numpy as np
 import torch
@@ -43,11 +46,48 @@ def rle_counts(rle):
     return vals.astype(np.uint32)
 
 
+RLE_CAP_COUNTS, RLE_CAP_CHARS = 4096, 16384      # first-try row capacities of the device encoder (a 1024^2 everything-mode mask has ~1e3 runs)
+
+
+def _rle_encode_device(masks):
+    """masks uint8 / bool [K, H, W] on the device -> (chars uint8 [K, cap] on the device, n_chars [K] on the host): `llmseg_rle_encode`, run
+    again with the true sizes it reports when a mask exceeds a capacity."""
+    K, H, W = masks.shape
+    m = (masks.to(torch.uint8) if masks.dtype == torch.bool else masks).contiguous()
+    assert m.dtype == torch.uint8, f"masks: uint8 or bool, got {m.dtype}"
+    dev, lib = m.device, _lib.load()
+    ws = torch.empty((int(lib.llmseg_rle_encode_ws_bytes(K, H, W)),), device=dev, dtype=torch.uint8)
+    sizes = torch.empty((2, K), device=dev, dtype=torch.int32)
+    cc, ch = RLE_CAP_COUNTS, RLE_CAP_CHARS
+    for attempt in range(2):
+        counts = torch.empty((K, cc), device=dev, dtype=torch.int32)
+        chars = torch.empty((K, ch), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            _lib.check(lib.llmseg_rle_encode(_p(m), K, H, W, _p(counts), _p(sizes[0]), cc, _p(chars), _p(sizes[1]), ch, _p(ws), ws.numel(), _stream()),
+                       "rle_encode")
+        n = sizes.cpu()
+        need_c, need_h = int(n[0].max()), int(n[1].max())
+        if need_c <= cc and need_h <= ch:
+            return chars, n[1]
+        assert attempt == 0, "rle_encode: the sizes of the first pass did not hold in the second"
+        cc, ch = max(cc, need_c), max(ch, need_h)
+
+
 def rle_encode_masks(masks):
     """uint8 / bool [K, H, W] (tensor or array) -> [{'size': [H, W], 'counts': str}]: pycocotools `mask.encode` output (maskApi rleEncode +
     rleToString: column-major runs starting with zeros; counts from the fourth on as deltas against the count two back; 5-bit groups, low
-    first, bit 5 = continuation, bit 4 of the last group = sign).  Host-side: this is the reference's FILE format (prepare_datasets/*),
-    the path itself consumes the dense masks."""
+    first, bit 5 = continuation, bit 4 of the last group = sign).  This is the reference's FILE format (prepare_datasets/*), the path itself
+    consumes the dense masks.  A device tensor is encoded on the device (`llmseg_rle_encode`) and only the valid characters are copied to
+    the host; a CPU tensor or an array is encoded on the host.  Both routes return the same value."""
+    if torch.is_tensor(masks) and masks.is_cuda:
+        K, H, W = masks.shape
+        if K == 0:
+            return []
+        chars, n = _rle_encode_device(masks.detach())
+        keep = torch.arange(chars.shape[1], device=chars.device)[None, :] < n.to(chars.device)[:, None]
+        flat = chars[keep].cpu().numpy().tobytes()                     # ONE copy: the K strings back to back
+        ends = np.cumsum(n.numpy().astype(np.int64)).tolist()
+        return [{"size": [int(H), int(W)], "counts": flat[e - int(l):e].decode("ascii")} for e, l in zip(ends, n.tolist())]
     m = masks.detach().cpu().numpy() if torch.is_tensor(masks) else np.asarray(masks)
     K, H, W = m.shape
     out = []
@@ -161,9 +201,37 @@ def _p(t):
     return C.c_void_p(t.data_ptr())
 
 
-def decode_rles(rles, device, hwk=False):
-    """list of COCO RLE dicts (same size) -> uint8 [K, H, W] (or [H, W, K], `mask_util.decode`'s layout) on the device."""
+def _parse_rles_device(strings, device):
+    """K compressed count strings (str / bytes) -> (run_ends int32 [total characters] (the uint32 bits; the first run_offsets[K] are valid),
+    run_offsets int64 [K + 1]) on the device, `llmseg_rle_decode`'s inputs: the host only joins the bytes; `llmseg_rle_parse` does the rest."""
+    bs = [c.encode("ascii") if isinstance(c, str) else bytes(c) for c in strings]
+    K = len(bs)
+    offs = np.zeros(K + 1, np.int64)
+    np.cumsum([len(b) for b in bs], out=offs[1:])
+    total = int(offs[-1])
+    dev, lib = torch.device(device), _lib.load()
+    d_chars = torch.from_numpy(np.frombuffer(b"".join(bs) or b"\0", dtype=np.uint8).copy()).to(dev)
+    d_offs = torch.from_numpy(offs).to(dev)
+    ends = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
+    run_offs = torch.empty((K + 1,), device=dev, dtype=torch.int64)
+    ws = torch.empty((int(lib.llmseg_rle_parse_ws_bytes(K, total)),), device=dev, dtype=torch.uint8)
+    _lib.check(lib.llmseg_rle_parse(_p(d_chars), _p(d_offs), K, _p(ends), _p(run_offs), _p(ws), ws.numel(), _stream()), "rle_parse")
+    return ends, run_offs
+
+
+def decode_rles(rles, device, hwk=False, host_parse=False):
+    """list of COCO RLE dicts (same size) -> uint8 [K, H, W] (or [H, W, K], `mask_util.decode`'s layout) on the device.  Compressed strings
+    (`counts` str / bytes) bound for a GPU are parsed there (`llmseg_rle_parse`); `host_parse=True`, a CPU device or any `list` counts take
+    the host parse (`rle_counts`)."""
     H, W = rles[0]["size"]
+    if not host_parse and torch.device(device).type == "cuda" and all(isinstance(r["counts"], (str, bytes)) for r in rles):
+        assert all(tuple(r["size"]) == (H, W) for r in rles)
+        K = len(rles)
+        with torch.cuda.device(torch.device(device)):
+            d_ends, d_offs = _parse_rles_device([r["counts"] for r in rles], device)
+            out = torch.empty((H, W, K) if hwk else (K, H, W), device=device, dtype=torch.uint8)
+            _lib.check(_lib.load().llmseg_rle_decode(_p(d_ends), _p(d_offs), _p(out), K, H, W, 1 if hwk else 0, _stream()), "rle_decode")
+        return out
     runs = [rle_counts(r) for r in rles]
     assert all(tuple(r["size"]) == (H, W) for r in rles)
     ends = np.concatenate([np.cumsum(r, dtype=np.uint64).astype(np.uint32) for r in runs])
@@ -210,6 +278,32 @@ def extract_sam_segs(masks, device, top=50):
     -> {"segs_origin": uint8 [K, H, W], "bbox": [...]} (the zero-padded square is never materialised: `resize_square_aa` pads on the fly)."""
     ms = sorted(masks, key=lambda m: m["area"], reverse=True)[:top]
     return {"segs_origin": decode_rles([m["segmentation"] for m in ms], device), "bbox": [m["bbox"] for m in ms]}
+
+
+class SamMaskReader:
+    """The reference's `SAM_Mask_Reader` (utils/sam_mask_reader.py) over a `masks.json` -- a list of {"image", "target_size", "masks": records},
+    what `llmseg_amd.prepare` and the reference's convert_h5_to_json.py write -- with the same method names; `extract_sam_segs` decodes on the device."""
+
+    def __init__(self, json_path):
+        self.json_dir = json_path
+        self.mask_list = self.read_mask_json(json_path)
+        self.sam_mask_index = self.build_sam_mask_index()
+
+    def read_mask_json(self, path):
+        with open(path, "r") as f:
+            return json.load(f)
+
+    def build_sam_mask_index(self):
+        return {sample["image"]: i for i, sample in enumerate(self.mask_list)}
+
+    def get_sam_mask_index(self, image_name):
+        if image_name not in self.sam_mask_index:
+            raise ValueError(f"image_name: {image_name} not in sam_mask_index")
+        return self.sam_mask_index[image_name]
+
+    def extract_sam_segs(self, image_name, device, top=50):
+        """sam_mask_reader.py:69-113 -> the module-level `extract_sam_segs` of that sample's records."""
+        return extract_sam_segs(self.mask_list[self.get_sam_mask_index(image_name)]["masks"], device, top)
 
 
 def _stack_targets(rows, K, dev):
