@@ -371,7 +371,7 @@ __device__ __forceinline__ void epilogue_fx(const GemmP& p, const ACC& acc, char
   } else {
     const int cc = lane & 7, r8 = lane >> 3;
     const int lcol = (FX == FX_ROPE ? (wn >> 1) * 128 + (wn & 1) * 32 : wn * 32) + cc * 4;      // tile-local column of the first element of the pair
-    const bool rot = FX == FX_ROPE && n0 < p.fx_cols;
+    const bool rot = FX == FX_ROPE && n0 + (wn >> 1) * 128 < p.fx_cols;      // per head: a tile holds two, and fx_cols may end between them
     const float inv_T = 1.f / (float)p.fx_T;
 #pragma unroll
     for (int i = 0; i < MI; ++i) {

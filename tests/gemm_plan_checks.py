@@ -5,6 +5,8 @@ A plan line is `label` followed by the plan's fields as key=value, or `label ref
 gemm_dispatch as they stood before gemm_plan.h existed (copied into a scratch program, launches replaced by records), not by gemm_plan: a change of
 the dispatch shows as a diff of that file."""
 import os
+import shutil
+import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "gemm_plans.txt")
@@ -190,6 +192,28 @@ def gpu_queries():
         query("gpu:skinny_ksplit", 5, 520, 2048),
         query("gpu:skinny", 5, 520, 256),
     ]
+
+
+def build_plan_program(tmp_dir):
+    """tests/gemm_plan_main.cpp as a stand-alone host program under AddressSanitizer and UBSan -> its path"""
+    assert shutil.which("g++"), "the plan program needs g++"
+    exe = os.path.join(str(tmp_dir), "gemm_plan_main")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", "-Werror",
+                           "-I", PLAN_HEADER_DIR, MAIN_CPP, "-o", exe])
+    return exe
+
+
+def run_plan_program(exe, query_lines):
+    """one plan line per query line"""
+    r = subprocess.run([exe], input="\n".join(query_lines) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, r.stderr[-2000:]
+    return r.stdout.splitlines()
+
+
+def parse_plan(line):
+    """label, {field: value} of one plan line (None: refused)"""
+    parts = line.split()
+    return parts[0], (None if parts[1:] == ["refused"] else dict(kv.split("=", 1) for kv in parts[1:]))
 
 
 def golden_plans():

@@ -3,8 +3,6 @@
 gemm_plan.h is host-only, so tests/gemm_plan_main.cpp is built with a plain g++ under AddressSanitizer and UBSan as a stand-alone program; it prints one plan
 line per query of tests/gemm_plan_checks.py.  The golden lines come from the dispatch as it stood before the header existed (see gemm_plan_checks)."""
 import ctypes as C
-import shutil
-import subprocess
 
 import pytest
 
@@ -13,13 +11,7 @@ from tests import gemm_plan_checks as gp
 
 @pytest.fixture(scope="module")
 def plan_lines(tmp_path_factory):
-    assert shutil.which("g++"), "the plan program needs g++"
-    exe = str(tmp_path_factory.mktemp("gemm_plan") / "gemm_plan_main")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", "-Werror",
-                           "-I", gp.PLAN_HEADER_DIR, gp.MAIN_CPP, "-o", exe])
-    r = subprocess.run([exe], input="\n".join(gp.queries()) + "\n", capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr, r.stderr[-2000:]
-    return r.stdout.splitlines()
+    return gp.run_plan_program(gp.build_plan_program(tmp_path_factory.mktemp("gemm_plan")), gp.queries())
 
 
 def test_plans_match_the_golden_file(plan_lines):
