@@ -31,10 +31,10 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * an entry point whose struct does not have exactly that size returns LLMSEG_EINVAL ("ABI mismatch") before reading any other field,
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
- * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args; -1 for an unknown index) so a binding can assert at load time;
+ * llmseg_version() is bumped whenever a struct or a signature changes (13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 12
+#define LLMSEG_ABI_VERSION 13
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -136,6 +136,35 @@ int llmseg_gemm_bf16(const llmseg_gemm_args* args, void* stream);
  * bits 4-7: XCD skew + 1 (0 = keep); bits 8-12: forced split-K slice count for variants 8 / 9 / 10 (0 = 1 slice);
  * nothing sits above bit 12: higher bits are ignored. */
 int llmseg_gemm_set_variant(int variant);
+
+/* ---- int8 weight-only decode (per-row scales) ------------------------------------------------
+ * The decode step of generation streams every decoder weight once per token (HBM-bound): int8 rows with one fp32 scale each halve
+ * the stream.  The reference offers 8-bit weights through bitsandbytes (its `--load_in_8bit` flag); this is NOT that arithmetic
+ * but the plain symmetric per-row quantiser below, stated exactly so that a caller can reproduce it bit for bit.
+ *
+ * llmseg_quantize_rows_i8: per row n of w [N][ldw] bf16 (finite values):
+ *   amax = max_k |w|;  scale[n] = amax / 127.0f;  inv = 127.0f / amax, 0 when amax == 0 (both divisions IEEE fp32);
+ *   q[n][k] = clamp(rintf((float)w * inv), -127, 127) (the product rounded once, ties to even), int8 two's complement [N][ldq];
+ *   w_hat[n][k] = bf16_rne((float)q * scale[n]), bf16 [N][ldh], written in the same pass when w_hat != NULL (the dequantised operand
+ *   of the prefill costs no extra read of w).
+ * K % 16 == 0, ldw % 8 == 0, ldh % 8 == 0, ldq % 16 == 0, every pointer 16-byte aligned.  One launch. */
+int llmseg_quantize_rows_i8(const void* w, int64_t ldw, int64_t N, int64_t K, void* q, int64_t ldq, float* scale, void* w_hat /* nullable */,
+                            int64_t ldh, void* stream);
+/* llmseg_gemm_w8: C[m][n] = residual[m][n] + scale[n] * sum_k A[m][k] * q[n][k], 1 <= M <= 8 (one token per sequence).
+ * A bf16 [M][lda], q int8 [N][ldq], fp32 FMA accumulation (a * q is exact in fp32), the scale applied once to the finished sum;
+ * C bf16 or fp32 (out_f32; ldc in elements of the output type).  K % 16 == 0, lda % 8 == 0, ldq % 16 == 0, A and q 16-byte aligned.
+ * A weight stream without MFMA, LDS staging or atomics: same inputs, same bits.  One launch. */
+typedef struct {
+  uint32_t struct_size;  /* = sizeof(llmseg_gemm_w8_args) of the caller's declaration (ABI guard, see above) */
+  uint32_t reserved0;    /* 0 */
+  const void* A; const void* Q; const float* scale;
+  const void* residual;  /* bf16 [M][ldr] or NULL */
+  void* C;
+  int64_t M, N, K;
+  int64_t lda, ldq, ldc, ldr;
+  int32_t out_f32; int32_t reserved1;
+} llmseg_gemm_w8_args;
+int llmseg_gemm_w8(const llmseg_gemm_w8_args* args, void* stream);
 
 /* ---- fused attention forward -----------------------------------------------------------------
  * O[b][h][q][:] = softmax_k( scale * Q.K^T + bias + mask ) V, online softmax in fp32, bf16 MFMA.

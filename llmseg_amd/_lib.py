@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 12         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 13         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
 NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
@@ -43,6 +43,12 @@ class GemmArgs(_Sized):
                 ("reserved2", C.c_int), ("nb_lora_drop", C.c_void_p),
                 ("dl_o", C.c_void_p), ("dl_ldo", C.c_int64), ("dl_out", C.c_void_p), ("dl_heads", C.c_int32), ("dl_T", C.c_int32),
                 ("nb_lora_part", C.c_void_p), ("nb_lora_S", C.c_int32), ("nb_lora_scale", C.c_float), ("nb_lora_zero", C.c_int32), ("reserved3", C.c_int32)]
+
+class GemmW8Args(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("A", C.c_void_p), ("Q", C.c_void_p), ("scale", C.c_void_p),
+                ("residual", C.c_void_p), ("C", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
+                ("lda", C.c_int64), ("ldq", C.c_int64), ("ldc", C.c_int64), ("ldr", C.c_int64), ("out_f32", C.c_int32), ("reserved1", C.c_int32)]
+
 
 FX_NONE, FX_ROPE, FX_SWIGLU, FX_SWIGLU_BWD = 0, 1, 2, 3          # LLMSEG_FX_* of include/llmseg_hip.h
 
@@ -84,6 +90,8 @@ SIGNATURES = {
     "llmseg_last_error": [],
     "llmseg_gemm_bf16": [C.POINTER(GemmArgs), _p],
     "llmseg_gemm_set_variant": [C.c_int],
+    "llmseg_quantize_rows_i8": [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p],
+    "llmseg_gemm_w8": [C.POINTER(GemmW8Args), _p],
     "llmseg_attn_fwd": [C.POINTER(AttnArgs), _p],
     "llmseg_attn_set_variant": [C.c_int],
     "llmseg_attn_bwd": [C.POINTER(AttnBwdArgs), _p],
@@ -186,7 +194,7 @@ def load():
     # ABI guard at load time: this binding's structs must be the library's (the entry points check `struct_size` per call as well)
     if lib.llmseg_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI version {lib.llmseg_version()} != {ABI_VERSION} of this binding (rebuild: llmseg_amd/csrc/build.sh)")
-    for which, st in enumerate((GemmArgs, AttnArgs, AttnBwdArgs, Dropout)):
+    for which, st in enumerate((GemmArgs, AttnArgs, AttnBwdArgs, Dropout, GemmW8Args)):
         if lib.llmseg_struct_size(which) != C.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) = {C.sizeof(st)} here, {lib.llmseg_struct_size(which)} in the library")
     _lib = lib

@@ -37,6 +37,8 @@ class DecodeState:
         self.graph = None
         self.fused = False           # decode step on merged-LoRA weights (+ norm / SwiGLU on the GEMM's A load for a single sequence)
         self.qkv_w = None            # per-layer q|k|v weights with the LoRA deltas merged in (fused steps)
+        self.bits = None             # weight_bits of the captured step (None = bf16 weights)
+        self.w8 = None               # weight_bits = 8: {layer-matrix name: (q int8, scale fp32, w_hat bf16)} of `_quantize_w8`
 
 
 class GenerateMixin:
@@ -145,26 +147,129 @@ class GenerateMixin:
         ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)
         st.pos.add_(1)
 
+    W8_MATRICES = ("qkv", "self_attn.o_proj.weight", "gate_up", "mlp.down_proj.weight")      # per layer, under "model.layers.{i}."
+
+    def _quantize_w8(self):
+        """weight_bits = 8: the four matrices of every layer (merged q|k|v with the LoRA deltas folded in, o_proj, gate|up, down_proj) as int8 rows
+        with one fp32 scale each, plus W^ = bf16(q * scale) for the prefill, from one `quantize_rows_i8` launch per matrix into persistent
+        buffers (6.5 GB + 13 GB at Llama-7B).  Rebuilt from the CURRENT weights at every call, as the merge is: weights loaded or trained in
+        place can never be stale.  The cost (merge included) is timed with a pair of events: `w8_prepare_ms()`."""
+        c = self.config.llama
+        F = _Direct
+        ev = self.__dict__.get("_w8_events")
+        if ev is None:
+            ev = self.__dict__["_w8_events"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        merged = self._merge_lora() if c.lora_r > 0 else None
+        bufs = self.__dict__.setdefault("_w8", {})
+        for i in range(c.layers):
+            p = f"model.layers.{i}."
+            src = (merged[i] if merged is not None else self._wcat(p + "qkv", [p + f"self_attn.{n}_proj.weight" for n in "qkv"], F),
+                   self._w(p + "self_attn.o_proj.weight", F),
+                   self._wcat(p + "gate_up", [p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], F),
+                   self._w(p + "mlp.down_proj.weight", F))
+            for name, w in zip(self.W8_MATRICES, src):
+                b = bufs.get(p + name)
+                if b is None:
+                    b = bufs[p + name] = (torch.empty(w.shape, device=w.device, dtype=torch.int8), torch.empty((w.shape[0],), device=w.device, dtype=torch.float32),
+                                          torch.empty_like(w))
+                ops.quantize_rows_i8(w, q=b[0], scale=b[1], w_hat=b[2])
+        ev[1].record()
+        return bufs
+
+    def w8_prepare_ms(self):
+        """Device time of the last `generate(weight_bits=8)` call's LoRA merge + quantisation (waits for that work to finish)."""
+        ev = self.__dict__["_w8_events"]
+        ev[1].synchronize()
+        return ev[0].elapsed_time(ev[1])
+
+    def decode_weights_i8(self):
+        """{layer-matrix name: (q int8 [N, K], scale fp32 [N])} of the last `generate(weight_bits=8)` call: names are "model.layers.{i}." +
+        "qkv" (merged q|k|v), "self_attn.o_proj.weight", "gate_up" (gate|up) and "mlp.down_proj.weight"."""
+        return {k: (b[0], b[1]) for k, b in self.__dict__["_w8"].items()}
+
+    def _prefill_w8(self, embeds, key_mask_u8, w8, kv_out):
+        """The prompt through the decoder stack of the QUANTISED model: the no-grad kernel sequence of `_llama` on W^ = bf16(q * scale), so that
+        prefill and decode steps run one model (the one a cache-free forward on the dequantised state dict runs).  -> final-norm hidden [N, T, H]."""
+        c = self.config.llama
+        F = _Direct
+        N, T, H = embeds.shape
+        x = embeds.reshape(N * T, H)
+        rope = self._rope(T)
+        for i in range(c.layers):
+            p = f"model.layers.{i}."
+            h = F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True)
+            qkv = ops.gemm(h, w8[p + "qkv"][2])
+            a = F.rope_attn(qkv, rope, N, T, c.heads, c.head_dim, True, key_mask_u8)
+            kv_out(i, qkv)                                     # qkv now holds the rotated K and V
+            x = ops.gemm(a, w8[p + "self_attn.o_proj.weight"][2], residual=x)
+            h = F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True)
+            gu = ops.gemm(h, w8[p + "gate_up"][2])
+            x = ops.gemm(ops.swiglu(gu, c.inter), w8[p + "mlp.down_proj.weight"][2], residual=x)
+        return F.norm(x, self._w("model.norm.weight", F), None, c.eps, True).view(N, T, H)
+
+    def _decode_body_w8(self, st):
+        """`_decode_body`'s fused step with `ops.gemm_w8` on the int8 rows in place of its four GEMMs; RMSNorm and SwiGLU are the separate
+        launches at every N (the A-load fusions of the bf16 route for a single sequence are not built for this kernel)."""
+        c = self.config.llama
+        F = _Direct
+        N, H = st.x.shape
+        cos, sin, _ = self._rope(st.cap)
+        hd, heads = c.head_dim, c.heads
+        x = st.x
+        att = torch.empty((N, H), device=x.device, dtype=BF16)
+        scratch = ops.decode_attn_scratch(N, heads, x.device) if hd == 128 else None
+        for i in range(c.layers):
+            p = f"model.layers.{i}."
+            q8 = lambda name: st.w8[p + name][:2]
+            qkv = ops.gemm_w8(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), *q8("qkv"))
+            if hd == 128:                                  # RoPE + KV append + attention over the cache: one launch (+ the split's merge)
+                ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
+            else:
+                ld = qkv.stride(0)
+                ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)
+                ops.attention(qkv, st.k[i], st.v[i], att, batch=N, heads=heads, Nq=1, Nk=st.cap, head_dim=hd, q_strides=(ld, hd, ld),
+                              k_strides=(st.cap * H, hd, H), v_strides=(st.cap * H, hd, H), o_strides=(H, hd, H), nk_dev=st.pos[1:])
+            x = ops.gemm_w8(att, *q8("self_attn.o_proj.weight"), residual=x)
+            gu = ops.gemm_w8(F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True), *q8("gate_up"))
+            x = ops.gemm_w8(ops.swiglu(gu, c.inter), *q8("mlp.down_proj.weight"), residual=x)
+        ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
+        ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)          # lm_head stays bf16: 2 % of the stream, and it decides the arg-max
+        st.pos.add_(1)
+
     def _decode_step(self, st, use_graph=True):
         """Run one decode step; from the second step of a state on, replay it from a hipGraph (captured once per (N, capacity): a step is
         ~420 launches of 5-20 us kernels, the host cannot issue them as fast as the GPU finishes them)."""
+        body = self._decode_body if st.bits is None else self._decode_body_w8
         if not use_graph:
-            return self._decode_body(st)
+            return body(st)
         if st.graph is None:
             if not getattr(st, "warm", False):
                 st.warm = True
-                return self._decode_body(st)                    # first step of this state: eager (also warms every allocation)
+                return body(st)                                 # first step of this state: eager (also warms every allocation)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):      # (another thread -- an RCCL watchdog -- may query events meanwhile: train.py::_capture)
-                self._decode_body(st)
+                body(st)
             st.graph = g                                        # capture records, it does not execute: fall through to the replay
         st.graph.replay()
 
     @torch.no_grad()
-    def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True):
+    def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
+                 weight_bits=None):
         """Greedy generation.  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
         IMAGE_TOKEN_INDEX each, no padding (evaluate() passes no attention mask).
-        -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last)."""
+        -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
+        weight_bits = 8 (opt-in; needs fuse_decode, the LoRA is merged first): the greedy continuation of the model whose four per-layer
+        matrices (merged q|k|v, o_proj, gate|up, down_proj) are W^ = q * scale, int8 rows with one fp32 scale each (`ops.quantize_rows_i8`);
+        lm_head, embeddings, norms, the KV cache and attention stay bf16.  The prefill runs on bf16(W^), the decode steps stream the int8 rows
+        (`ops.gemm_w8`): half the bytes of a step.  The weights are re-quantised at every call (`w8_prepare_ms()` gives the cost);
+        `decode_weights_i8()` returns them.  Measured at Llama-7B (profiles/w8_decode.md): 2.70 / 2.85 / 3.40 / 4.97 ms per token at 1 / 2 / 4 / 8 sequences
+        against 3.33 / 3.88 / 4.33 / 5.08 in bf16 -- at 8 sequences there is no gain (the int8 kernel takes as long as the bf16 kernel there, whatever
+        the FMA form) -- and 9.4 ms per call for the merge + quantisation, repaid after about 11 tokens at one sequence."""
+        if weight_bits not in (None, 8):
+            raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
+        if weight_bits == 8 and not fuse_decode:
+            raise ValueError("weight_bits=8 needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
         self.prepare()
         c = self.config
         cl = c.llama
@@ -186,11 +291,16 @@ class GenerateMixin:
         def keep_kv(i, qkv):                                   # qkv [N*T, 3H] after the in-place RoPE of q and k
             st.k[i, :, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
             st.v[i, :, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
-        hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)          # [N, T, H]
+        if weight_bits is None:
+            st.w8 = None
+            hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
+        else:
+            st.w8 = self._quantize_w8()
+            hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
         fused = bool(fuse_decode)
-        if fused != st.fused:
-            st.fused, st.graph, st.warm = fused, None, False                      # a different kernel sequence: capture again
-        st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0) else None
+        if fused != st.fused or weight_bits != st.bits:
+            st.fused, st.bits, st.graph, st.warm = fused, weight_bits, None, False      # a different kernel sequence: capture again
+        st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0 and weight_bits is None) else None
         st.pos.copy_(torch.tensor([T, T + 1], dtype=torch.int32))
         hidden = torch.empty((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
         hidden[:, :T] = hidden_p

@@ -163,6 +163,50 @@ def gemm(a, w, bias=None, act=ACT_NONE, residual=None, gamma=None, out=None, alp
     return out
 
 
+def quantize_rows_i8(w, want_hat=False, q=None, scale=None, w_hat=None):
+    """Per-row symmetric int8 quantisation of w [N, K] bf16 (K % 16 == 0, rows 16-byte aligned): -> (q int8 [N, K], scale fp32 [N]) and, with
+    want_hat, w_hat bf16 [N, K] = bf16(q * scale) from the same pass.  scale = amax / 127, q = clamp(rint(w * (127 / amax)), +-127) (0 for an
+    all-zero row); the arithmetic is stated in include/llmseg_hip.h.  q / scale / w_hat: existing buffers to write into (w_hat implies want_hat)."""
+    _req(w)
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    if q is None:
+        q = torch.empty((N, K), device=w.device, dtype=torch.int8)
+    if scale is None:
+        scale = torch.empty((N,), device=w.device, dtype=torch.float32)
+    if w_hat is None and want_hat:
+        w_hat = torch.empty((N, K), device=w.device, dtype=BF16)
+    assert q.is_cuda and q.dtype == torch.int8 and q.shape == (N, K) and q.stride(1) == 1
+    assert scale.is_cuda and scale.dtype == torch.float32 and scale.shape == (N,) and scale.is_contiguous()
+    assert w_hat is None or (_req(w_hat).shape == (N, K) and w_hat.stride(1) == 1)
+    _lib.check(_lib.load().llmseg_quantize_rows_i8(_ptr(w), w.stride(0), N, K, _ptr(q), q.stride(0), _ptr(scale), _ptr(w_hat),
+                                                   0 if w_hat is None else w_hat.stride(0), _stream()), "quantize_rows_i8")
+    return (q, scale, w_hat) if w_hat is not None else (q, scale)
+
+
+def gemm_w8(a, q, scale, residual=None, out=None, out_f32=False):
+    """out[M, N] = residual + scale[n] * (a [M, K] bf16 @ q [N, K] int8 ^T), M <= 8: the decode step's weight stream on int8 rows with one fp32
+    scale each (`quantize_rows_i8`).  fp32 accumulation, the scale applied once to the finished sum; out bf16, or fp32 with out_f32."""
+    _req(a)
+    assert a.dim() == 2 and q.dim() == 2 and a.stride(1) == 1 and q.stride(1) == 1 and q.is_cuda and q.dtype == torch.int8
+    M, K = a.shape
+    N = q.shape[0]
+    assert q.shape[1] == K and M <= 8, (a.shape, q.shape)
+    assert scale.is_cuda and scale.dtype == torch.float32 and scale.shape == (N,) and scale.is_contiguous()
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else BF16)
+    else:
+        out_f32 = out.dtype == torch.float32
+    assert out.shape == (M, N) and out.stride(1) == 1 and (out_f32 or out.dtype == BF16)
+    if residual is not None:
+        assert _req(residual).shape == (M, N) and residual.stride(1) == 1
+    g = _lib.GemmW8Args(A=a.data_ptr(), Q=q.data_ptr(), scale=scale.data_ptr(), residual=None if residual is None else residual.data_ptr(), C=out.data_ptr(),
+                        M=M, N=N, K=K, lda=a.stride(0), ldq=q.stride(0), ldc=out.stride(0), ldr=0 if residual is None else residual.stride(0),
+                        out_f32=1 if out_f32 else 0)
+    _lib.check(_lib.load().llmseg_gemm_w8(C.byref(g), _stream()), "gemm_w8")
+    return out
+
+
 def gemm_batched(a, w, out, M, N, K, lda, ldw, ldc, batch, sA, sW, sC, out_f32=True, alpha=1.0, trans_a=False, trans_w=False,
                  batch2=1, sA2=0, sW2=0, sC2=0):
     """Strided-batched GEMM on raw strides (elements); used for the per-head q.R^T relative-position products."""
