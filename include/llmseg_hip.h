@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 13
+#define LLMSEG_ABI_VERSION 14
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -277,6 +277,13 @@ int llmseg_rope_kv_append(void* qkv, int64_t ld, const float* cos, const float* 
 int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                        const int32_t* pos_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
                        void* scratch, int64_t scratch_bytes, void* stream);
+/* llmseg_decode_attn with one position per sequence (a batch whose prompts differ in length): pos_rows_dev int32 [N] in device memory, and
+ * sequence n uses pos = pos_rows_dev[n] for everything llmseg_decode_attn derives from *pos_dev -- the RoPE angle of its q and k, the
+ * cache slot kcache[n][pos] / vcache[n][pos] it writes, and the pos + 1 keys it attends to.  Cache slots beyond a sequence's own position
+ * are neither read nor written.  Same kernel, same argument checks, same scratch; equal positions give the bits of llmseg_decode_attn. */
+int llmseg_decode_attn_rows(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                            const int32_t* pos_rows_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
+                            void* scratch, int64_t scratch_bytes, void* stream);
 
 /* y[i] = act(x[i]), bf16, n % 8 == 0, in place allowed (the GELU between LayerNorm2d and the second transposed convolution of SAM's
  * mask decoder, mask_decoder.py:53-63: every other activation on the path rides in a GEMM epilogue) */

@@ -1227,7 +1227,7 @@ struct DecP {
   const bf16_t* qkv; long ld;
   const float *cs, *sn;
   bf16_t *kc, *vc; long cstride;
-  const int32_t* pos_dev;
+  const int32_t* pos_dev; long pos_stride;           // position of sequence n: pos_dev[n * pos_stride] (0: one position for every sequence)
   int heads, splits;
   float scale;
   bf16_t* out; long ldo;
@@ -1242,7 +1242,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = tid >> 4, c = tid & 15;
   const int h = blockIdx.x / p.splits, sp = blockIdx.x - h * p.splits, n = blockIdx.y;
   const long D = (long)p.heads * HD;
-  const int pos = *p.pos_dev, nk = pos + 1;
+  const int pos = p.pos_dev[(long)n * p.pos_stride], nk = pos + 1;      // workgroup-uniform: a scalar load
   const int per = ((nk + p.splits - 1) / p.splits + 15) & ~15;
   const int j0 = sp * per, j1 = min(nk, j0 + per);
   const bool owner = pos >= j0 && pos < j1;              // the workgroup whose key range holds the new token appends it
@@ -1348,9 +1348,10 @@ __global__ __launch_bounds__(128) void decode_attn_merge_kernel(const float* __r
   out[(long)n * ldo + (long)h * 128 + tid] = f2bf(o / L);
 }
 
-extern "C" int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
-                                  const int32_t* pos_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
-                                  void* scratch, int64_t scratch_bytes, void* stream) {
+namespace {
+int decode_attn_launch(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                       const int32_t* pos_dev, long pos_stride, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
+                       void* scratch, int64_t scratch_bytes, void* stream) {
   LL_CHECK(qkv && cos && sin && kcache && vcache && pos_dev && out && N > 0 && N < 65536 && heads > 0, "decode_attn: bad arguments");
   LL_CHECK(head_dim == 128, "decode_attn: head_dim 128 only (use llmseg_rope_kv_append + llmseg_attn_fwd otherwise)");
   LL_CHECK((ld & 7) == 0 && (cache_stride_n & 7) == 0 && AL16(qkv) && AL16(kcache) && AL16(vcache), "decode_attn: 16-byte alignment required");
@@ -1359,7 +1360,7 @@ extern "C" int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos,
     splits = (int)std::min<int64_t>(16, std::max<int64_t>(1, 256 / (N * heads)));
     while (splits > 1 && (int64_t)N * heads * splits * 130 * 4 > scratch_bytes) --splits;
   }
-  DecP p{(const bf16_t*)qkv, (long)ld, cos, sin, (bf16_t*)kcache, (bf16_t*)vcache, (long)cache_stride_n, pos_dev, heads, splits, scale,
+  DecP p{(const bf16_t*)qkv, (long)ld, cos, sin, (bf16_t*)kcache, (bf16_t*)vcache, (long)cache_stride_n, pos_dev, pos_stride, heads, splits, scale,
          (bf16_t*)out, (long)ldo, (float*)scratch};
   LL_LAUNCH_KERNEL(decode_attn_kernel, dim3(heads * splits, (unsigned)N), dim3(256), 0, (hipStream_t)stream, p);
   LL_LAUNCH_CHECK("decode_attn");
@@ -1369,6 +1370,20 @@ extern "C" int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos,
     LL_LAUNCH_CHECK("decode_attn_merge");
   }
   return LLMSEG_OK;
+}
+}  // namespace
+
+extern "C" int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                                  const int32_t* pos_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
+                                  void* scratch, int64_t scratch_bytes, void* stream) {
+  return decode_attn_launch(qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_dev, 0, N, heads, head_dim, scale, out, ldo, scratch, scratch_bytes, stream);
+}
+
+// one position per sequence (prompts of unequal length): the same kernel, which reads pos_rows_dev[n]
+extern "C" int llmseg_decode_attn_rows(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                                       const int32_t* pos_rows_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
+                                       void* scratch, int64_t scratch_bytes, void* stream) {
+  return decode_attn_launch(qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_rows_dev, 1, N, heads, head_dim, scale, out, ldo, scratch, scratch_bytes, stream);
 }
 
 extern "C" int llmseg_attn_set_variant(int v) {

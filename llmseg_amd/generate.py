@@ -9,6 +9,8 @@ MI355X-first shape of the loop:
   * a decode step feeds ONE token per sequence: RMSNorm -> q|k|v GEMM (+LoRA) on N rows -> RoPE at the step's position -> K, V rows
     appended to the cache -> attention of the single query over the cache (`llmseg_attn_fwd`, Nq = 1, strided K / V) -> o_proj -> MLP.
     At N <= 8 rows every GEMM is a weight stream (13.5 GB per token): HBM-bound, not MFMA-bound;
+  * prompts of different lengths share a batch (`attention_mask`, right padding): the prefill masks the padding as training does, and every decode
+    step runs each sequence at its own device-side position (RoPE angle, cache slot, key count: `llmseg_decode_attn_rows`);
   * the reference generates WITHOUT a cache in its shipped configuration (`use_cache = False`) and reads the hidden states of its last
     forward; the cache yields the same tensor step by step (oracle/generate.py explains the equivalence and pins it).
 HF greedy-search rules restated from `transformers==4.29.0 generation/utils.py::greedy_search` (third party): finished rows emit
@@ -17,19 +19,34 @@ HF greedy-search rules restated from `transformers==4.29.0 generation/utils.py::
 import torch
 
 from . import ops
-from .trainable import _Direct
+from .trainable import IMAGE_TOKEN_INDEX, _Direct
 
 BF16 = torch.bfloat16
 
 
+def pad_prompts(prompts, pad_token_id=0):
+    """Prompts of different lengths (1-D id tensors, one <image> token each) -> (input_ids int64 [N, L], attention_mask bool [N, L]) for
+    `generate(..., attention_mask=)`: right padding with `pad_token_id` (0 if None), L = the longest prompt."""
+    assert len(prompts) > 0 and all(t.dim() == 1 and t.numel() > 0 for t in prompts)
+    L = max(int(t.numel()) for t in prompts)
+    ids = torch.full((len(prompts), L), 0 if pad_token_id is None else int(pad_token_id), dtype=torch.int64, device=prompts[0].device)
+    mask = torch.zeros((len(prompts), L), dtype=torch.bool, device=prompts[0].device)
+    for i, t in enumerate(prompts):
+        ids[i, :t.numel()] = t
+        mask[i, :t.numel()] = True
+    return ids, mask
+
+
 class DecodeState:
     """Everything a decode step touches, at fixed addresses (so the step can be captured once and replayed): the KV cache
-    [layers][N, capacity, H] bf16 x 2, the device-side position {pos, pos + 1}, the step's input embeddings and its outputs."""
+    [layers][N, capacity, H] bf16 x 2, the device-side position {pos, pos + 1} (or one position per sequence, pos_rows, when the prompts
+    differ in length), the step's input embeddings and its outputs."""
 
     def __init__(self, layers, N, cap, H, V, device):
         self.k = torch.empty((layers, N, cap, H), device=device, dtype=BF16)
         self.v = torch.empty((layers, N, cap, H), device=device, dtype=BF16)
         self.pos = torch.zeros((2,), device=device, dtype=torch.int32)       # [0] = position of the token being fed, [1] = keys present after it
+        self.pos_rows = torch.zeros((N,), device=device, dtype=torch.int32)  # ragged prompts: position of the token being fed, per sequence
         self.x = torch.empty((N, H), device=device, dtype=BF16)
         self.hidden = torch.empty((N, H), device=device, dtype=BF16)
         self.logits = torch.empty((N, V), device=device, dtype=BF16)
@@ -38,6 +55,7 @@ class DecodeState:
         self.fused = False           # decode step on merged-LoRA weights (+ norm / SwiGLU on the GEMM's A load for a single sequence)
         self.qkv_w = None            # per-layer q|k|v weights with the LoRA deltas merged in (fused steps)
         self.bits = None             # weight_bits of the captured step (None = bf16 weights)
+        self.ragged = False          # the captured step reads pos_rows (one position per sequence) instead of pos
         self.w8 = None               # weight_bits = 8: {layer-matrix name: (q int8, scale fp32, w_hat bf16)} of `_quantize_w8`
 
 
@@ -95,7 +113,10 @@ class GenerateMixin:
                 else:
                     qkv = ops.gemm(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), wq)
                 if hd == 128:                                  # RoPE + KV append + attention over the cache: one launch (+ the split's merge)
-                    ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
+                    if st.ragged:                              # every sequence at its own position: RoPE angle, cache slot and key count
+                        ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True)
+                    else:
+                        ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
                 else:
                     ld = qkv.stride(0)
                     ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)
@@ -113,7 +134,7 @@ class GenerateMixin:
                     x = ops.gemm(ops.swiglu(gu, c.inter), self._w(p + "mlp.down_proj.weight", F), residual=x)
             ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
             ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)
-            st.pos.add_(1)
+            (st.pos_rows if st.ragged else st.pos).add_(1)
             return
         cos, sin, _ = self._rope(st.cap)
         s = c.lora_alpha / c.lora_r if c.lora_r > 0 else 0.0
@@ -224,7 +245,10 @@ class GenerateMixin:
             q8 = lambda name: st.w8[p + name][:2]
             qkv = ops.gemm_w8(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), *q8("qkv"))
             if hd == 128:                                  # RoPE + KV append + attention over the cache: one launch (+ the split's merge)
-                ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
+                if st.ragged:
+                    ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True)
+                else:
+                    ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
             else:
                 ld = qkv.stride(0)
                 ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)
@@ -235,7 +259,7 @@ class GenerateMixin:
             x = ops.gemm_w8(ops.swiglu(gu, c.inter), *q8("mlp.down_proj.weight"), residual=x)
         ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
         ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)          # lm_head stays bf16: 2 % of the stream, and it decides the arg-max
-        st.pos.add_(1)
+        (st.pos_rows if st.ragged else st.pos).add_(1)
 
     def _decode_step(self, st, use_graph=True):
         """Run one decode step; from the second step of a state on, replay it from a hipGraph (captured once per (N, capacity): a step is
@@ -255,10 +279,17 @@ class GenerateMixin:
 
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
-                 weight_bits=None):
+                 weight_bits=None, attention_mask=None):
         """Greedy generation.  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
-        IMAGE_TOKEN_INDEX each, no padding (evaluate() passes no attention mask).
+        IMAGE_TOKEN_INDEX each.
         -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
+        attention_mask (bool [N, L], None = every token is a prompt token): prompts of different lengths, RIGHT-padded (`pad_prompts` builds
+        the pair).  Row i is its first L_i = attention_mask[i].sum() tokens and must hold its <image> token among them; both tensors are
+        trimmed to Lm = max L_i, and a mask that is all True after that is the call without a mask (the same kernels on the same route).
+        Otherwise every decode step runs each sequence at its own position (`llmseg_decode_attn_rows`: head_dim 128 and fuse_decode only),
+        and both results are packed per row, left-aligned: sequences [N, Lm + n_new] holds row i's prompt, its n_new new tokens, then
+        pad_token_id (0 if None); hidden [N, Tm + n_new - 1, H] holds row i's T_i = L_i - 1 + n_img_tokens prefill states, the state of its
+        k-th fed token at T_i + k - 1, then zeros -- the layout `seg_embeddings` reads.
         weight_bits = 8 (opt-in; needs fuse_decode, the LoRA is merged first): the greedy continuation of the model whose four per-layer
         matrices (merged q|k|v, o_proj, gate|up, down_proj) are W^ = q * scale, int8 rows with one fp32 scale each (`ops.quantize_rows_i8`);
         lm_head, embeddings, norms, the KV cache and attention stay bf16.  The prefill runs on bf16(W^), the decode steps stream the int8 rows
@@ -274,11 +305,22 @@ class GenerateMixin:
         c = self.config
         cl = c.llama
         dev = self.device_
+        lens = None                                            # prompt lengths L_i on the host, ragged calls only
+        if attention_mask is not None:
+            input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
+        if lens is not None:
+            if not fuse_decode:
+                raise ValueError("prompts of different lengths need fuse_decode=True (the per-row positions are built into the fused decode step only)")
+            if cl.head_dim != 128:
+                raise ValueError(f"prompts of different lengths need head_dim 128, got {cl.head_dim}: per-row key counts for the two-launch "
+                                 "route (llmseg_rope_kv_append + llmseg_attn_fwd) are out of scope")
+            fill = 0 if pad_token_id is None else int(pad_token_id)
+            input_ids = torch.where(attention_mask.to(input_ids.device), input_ids, torch.full_like(input_ids, fill))
         N, L = input_ids.shape
         Pn, H = c.n_img_tokens, cl.hidden
         T = L - 1 + Pn
         assert max_new_tokens >= 1
-        plan = self.make_plan(input_ids, None, torch.ones((N, L), dtype=torch.bool), list(range(N + 1)), None, inference=False)
+        plan = self.make_plan(input_ids, None, torch.ones((N, L), dtype=torch.bool) if lens is None else attention_mask, list(range(N + 1)), None, inference=False)
         F = _Direct
         proj = self.encode_images(images_clip.to(dev, BF16))
         embeds = F.embed_splice(input_ids.to(dev).contiguous(), self._w("model.embed_tokens.weight", F), proj[1:], Pn, (Pn + 1) * H, plan.tok_index)
@@ -288,6 +330,9 @@ class GenerateMixin:
         if st is None:
             st = states[(N, cap)] = DecodeState(cl.layers, N, cap, H, cl.vocab, dev)
 
+        # ragged prompts: K and V are copied for [:, :T] of every row.  The slots at or beyond a row's own T_i = L_i - 1 + Pn then hold the padding's
+        # K / V (and, past T, whatever an earlier call left): garbage that is never read, because the step that feeds a row's token at position
+        # pos writes cache[pos] itself and attends to keys 0 .. pos only -- a slot is overwritten before the row's key count reaches it.
         def keep_kv(i, qkv):                                   # qkv [N*T, 3H] after the in-place RoPE of q and k
             st.k[i, :, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
             st.v[i, :, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
@@ -298,14 +343,25 @@ class GenerateMixin:
             st.w8 = self._quantize_w8()
             hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
         fused = bool(fuse_decode)
-        if fused != st.fused or weight_bits != st.bits:
-            st.fused, st.bits, st.graph, st.warm = fused, weight_bits, None, False      # a different kernel sequence: capture again
+        ragged = lens is not None
+        if fused != st.fused or weight_bits != st.bits or ragged != st.ragged:
+            st.fused, st.bits, st.ragged, st.graph, st.warm = fused, weight_bits, ragged, None, False      # a different kernel sequence: capture again
         st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0 and weight_bits is None) else None
-        st.pos.copy_(torch.tensor([T, T + 1], dtype=torch.int32))
-        hidden = torch.empty((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
-        hidden[:, :T] = hidden_p
         emb_w = self._w("model.embed_tokens.weight", F)
-        logits = ops.gemm(hidden_p[:, -1].contiguous(), self._w("lm_head.weight", F))     # only the last position's logits are needed
+        if ragged:
+            t_rows = (lens - 1 + Pn).to(dev)                    # T_i: row i's prefill length = the position of its first fed token
+            st.pos_rows.copy_(t_rows.to(torch.int32))
+            hidden = torch.zeros((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
+            own = torch.arange(T, device=dev)[None, :] < t_rows[:, None]
+            hidden[:, :T] = torch.where(own[:, :, None], hidden_p, torch.zeros_like(hidden_p))
+            last = torch.arange(N, device=dev) * T + t_rows - 1                            # each row's own last prompt position
+            logits = ops.gemm(ops.gather_rows(hidden_p.reshape(N * T, H), last), self._w("lm_head.weight", F))
+            slot = torch.arange(N, device=dev) * hidden.shape[1] + t_rows - 1                # flat row of `hidden` that holds each sequence's newest state
+        else:
+            st.pos.copy_(torch.tensor([T, T + 1], dtype=torch.int32))
+            hidden = torch.empty((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
+            hidden[:, :T] = hidden_p
+            logits = ops.gemm(hidden_p[:, -1].contiguous(), self._w("lm_head.weight", F))     # only the last position's logits are needed
         seqs = [input_ids.to(dev)]
         unfinished = torch.ones((N,), dtype=torch.int64, device=dev)
         n_new = 0
@@ -323,9 +379,37 @@ class GenerateMixin:
                 break
             st.x.copy_(ops.gather_rows(emb_w, nxt))
             self._decode_step(st, use_graph)
-            hidden[:, T + n_new - 1] = st.hidden
+            if ragged:
+                hidden.view(-1, H).index_copy_(0, slot.add_(1), st.hidden)
+            else:
+                hidden[:, T + n_new - 1] = st.hidden
             logits = st.logits
+        if ragged:                                             # row i: prompt, new tokens, fill
+            out = torch.cat([seqs[0], torch.full((N, n_new), fill, dtype=torch.int64, device=dev)], 1)
+            out.scatter_(1, lens.to(dev)[:, None] + torch.arange(n_new, device=dev)[None, :], torch.cat(seqs[1:], 1))
+            return out, hidden[:, :T + n_new - 1]
         return torch.cat(seqs, 1), hidden[:, :T + n_new - 1]
+
+    @staticmethod
+    def _ragged_prompts(input_ids, attention_mask):
+        """Checks of `generate(attention_mask=)` -> (input_ids, attention_mask, lens) trimmed to the longest prompt; (input_ids, None, None) when
+        every row is full after trimming (the uniform route)."""
+        if not torch.is_tensor(attention_mask) or attention_mask.dtype != torch.bool or attention_mask.shape != input_ids.shape or input_ids.dim() != 2:
+            raise ValueError(f"attention_mask must be a bool tensor of input_ids' shape {tuple(input_ids.shape)}, got "
+                             f"{getattr(attention_mask, 'dtype', type(attention_mask))} {tuple(getattr(attention_mask, 'shape', ()))}")
+        am = attention_mask.detach().cpu()
+        ids = input_ids.detach().cpu()
+        lens = am.sum(1)
+        if not torch.equal(am, torch.arange(am.shape[1])[None, :] < lens[:, None]):
+            raise ValueError("attention_mask must be right padding: every row a prefix of True (no holes, no left padding)")
+        is_img = (ids == IMAGE_TOKEN_INDEX) & am
+        if not bool((is_img.sum(1) == 1).all()):
+            raise ValueError("every row must hold its one <image> token inside its own prompt (attention_mask cuts it off, or the row is empty)")
+        Lm = int(lens.max())
+        input_ids = input_ids[:, :Lm]
+        if bool((lens == Lm).all()):
+            return input_ids, None, None
+        return input_ids, am[:, :Lm].contiguous(), lens
 
     @torch.no_grad()
     def seg_embeddings(self, output_ids, hidden):
