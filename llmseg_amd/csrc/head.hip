@@ -335,17 +335,24 @@ __global__ __launch_bounds__(256) void ce_kernel(const bf16_t* __restrict__ logi
 
 // SAM mask post-processing (sam.py:137-172): low-res logits 256 x 256 -> bilinear (align_corners = False) to img x img, crop to the
 // input size, bilinear to the original size, all in fp32 -- fused: every output pixel evaluates its four stage-1 samples on the fly
-// (16 reads of a 256 KiB mask that lives in L2).  torch's upsample_bilinear2d arithmetic: src = max(0, scale (o + 0.5) - 0.5),
+// (16 reads of a 256 KiB mask that lives in L2).  torch's upsample_bilinear2d arithmetic: src = max(0, fma(scale, o + 0.5, -0.5)),
 // i0 = floor(src), i1 = i0 + (i0 < in - 1), weights (1 - frac, frac), value = w_y0 (w_x0 v00 + w_x1 v01) + w_y1 (w_x0 v10 + w_x1 v11).
 // `nested` = the layout the two stride-2 transposed convolutions of the mask decoder leave when run as GEMMs on token-major rows:
 // pixel (Y, X) sits at ((y 64 + x) 4 + dy1 2 + dx1) 4 + dy2 2 + dx2 with Y = 4 y + 2 dy1 + dy2 (no pixel-shuffle pass is needed).
+// The compiler's default contracts a * b + c into one fma wherever it sees one, through __fmul_rn / __fadd_rn as well (the header defines them as
+// plain operators).  Contraction is off from here to the end of sam_binarize_kernel, so that the three kernels perform exactly the operations stated
+// above, each rounded once: tests/test_amg_kernels_gpu.py holds them to an fp32 emulation bit for bit and to each other exactly.  The one fma that
+// torch's own kernels do perform, in the source coordinate, is spelled out (profiles/amg_parity.md).
+#pragma clang fp contract(off)
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }      // one rounding each: never half of an fma
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
 __device__ __forceinline__ float sam_low(const float* __restrict__ m, int Y, int X, int nested) {
   if (!nested) return m[Y * 256 + X];
   const int tok = (Y >> 2) * 64 + (X >> 2);
   return m[(tok * 4 + ((Y >> 1) & 1) * 2 + ((X >> 1) & 1)) * 4 + (Y & 1) * 2 + (X & 1)];
 }
 __device__ __forceinline__ void bil_coord(int o, float scale, int in, int& i0, int& i1, float& w0, float& w1) {
-  const float src = fmaxf(0.f, __fmul_rn(scale, (float)o + 0.5f) - 0.5f);
+  const float src = fmaxf(0.f, fmaf(scale, (float)o + 0.5f, -0.5f));      // one rounding, as torch's own kernels compile this expression
   i0 = (int)src;
   i1 = i0 + (i0 < in - 1 ? 1 : 0);
   w1 = src - (float)i0;
@@ -367,11 +374,11 @@ __global__ __launch_bounds__(256) void sam_postprocess_kernel(const float* __res
     float u0, u1, v0, v1;
     bil_coord(Y, s1, 256, a0, a1, u0, u1);
     bil_coord(X, s1, 256, c0, c1, v0, v1);
-    return __fadd_rn(__fmul_rn(u0, __fadd_rn(__fmul_rn(v0, sam_low(m, a0, c0, nested)), __fmul_rn(v1, sam_low(m, a0, c1, nested)))),
-                     __fmul_rn(u1, __fadd_rn(__fmul_rn(v0, sam_low(m, a1, c0, nested)), __fmul_rn(v1, sam_low(m, a1, c1, nested)))));
+    return add_rn(mul_rn(u0, add_rn(mul_rn(v0, sam_low(m, a0, c0, nested)), mul_rn(v1, sam_low(m, a0, c1, nested)))),
+                  mul_rn(u1, add_rn(mul_rn(v0, sam_low(m, a1, c0, nested)), mul_rn(v1, sam_low(m, a1, c1, nested)))));
   };
-  const float r = __fadd_rn(__fmul_rn(wy0, __fadd_rn(__fmul_rn(wx0, stage1(y0, x0)), __fmul_rn(wx1, stage1(y0, x1)))),
-                            __fmul_rn(wy1, __fadd_rn(__fmul_rn(wx0, stage1(y1, x0)), __fmul_rn(wx1, stage1(y1, x1)))));
+  const float r = add_rn(mul_rn(wy0, add_rn(mul_rn(wx0, stage1(y0, x0)), mul_rn(wx1, stage1(y0, x1)))),
+                         mul_rn(wy1, add_rn(mul_rn(wx0, stage1(y1, x0)), mul_rn(wx1, stage1(y1, x1)))));
   out[((long)b * oh + oy) * ow + ox] = r;
 }
 
@@ -449,10 +456,10 @@ __device__ __forceinline__ float post_value(const float* __restrict__ m, const P
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-      s[i][j] = __fadd_rn(__fmul_rn(r.u[i][0], __fadd_rn(__fmul_rn(c.v[j][0], k.L[i][0][j][0]), __fmul_rn(c.v[j][1], k.L[i][0][j][1]))),
-                          __fmul_rn(r.u[i][1], __fadd_rn(__fmul_rn(c.v[j][0], k.L[i][1][j][0]), __fmul_rn(c.v[j][1], k.L[i][1][j][1]))));
-  return __fadd_rn(__fmul_rn(r.w[0], __fadd_rn(__fmul_rn(c.w[0], s[0][0]), __fmul_rn(c.w[1], s[0][1]))),
-                   __fmul_rn(r.w[1], __fadd_rn(__fmul_rn(c.w[0], s[1][0]), __fmul_rn(c.w[1], s[1][1]))));
+      s[i][j] = add_rn(mul_rn(r.u[i][0], add_rn(mul_rn(c.v[j][0], k.L[i][0][j][0]), mul_rn(c.v[j][1], k.L[i][0][j][1]))),
+                       mul_rn(r.u[i][1], add_rn(mul_rn(c.v[j][0], k.L[i][1][j][0]), mul_rn(c.v[j][1], k.L[i][1][j][1]))));
+  return add_rn(mul_rn(r.w[0], add_rn(mul_rn(c.w[0], s[0][0]), mul_rn(c.w[1], s[0][1]))),
+                mul_rn(r.w[1], add_rn(mul_rn(c.w[0], s[1][0]), mul_rn(c.w[1], s[1][1]))));
 }
 constexpr int POST_ROWS = 64;
 
@@ -513,6 +520,8 @@ __global__ __launch_bounds__(256) void sam_binarize_kernel(const float* __restri
   for (int r = 0; r < nrow; ++r) o[(long)r * ow] = post_value(m, rows[r], pc, pk) > thr ? 1 : 0;
 }
 
+#pragma clang fp contract(fast)
+
 // Greedy box NMS (torchvision.ops.nms semantics, one category): `order` = candidate indices by decreasing score; keep[i] = 1 if box
 // order[i] survives: a kept box suppresses every later box with IoU > thr, areas (x2 - x1)(y2 - y1).  One workgroup; n <= 8192.
 __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ order, int n, float thr, uint8_t* __restrict__ keep) {
@@ -549,8 +558,9 @@ extern "C" int llmseg_sam_mask_stats(const float* low, const float* iou, float i
 
 extern "C" int llmseg_sam_binarize(const float* low, const int32_t* sel, uint8_t* out, int32_t n_sel, int32_t img_size, int32_t in_h, int32_t in_w, int32_t out_h,
                                    int32_t out_w, int32_t nested, float mask_threshold, void* stream) {
-  LL_CHECK(low && sel && out && n_sel > 0 && img_size > 0 && in_h > 0 && in_w > 0 && out_h > 0 && out_w > 0, "sam_binarize: bad arguments");
-  LL_CHECK(n_sel < 65536, "sam_binarize: grid limit");
+  LL_CHECK(low && sel && out && n_sel > 0 && img_size > 0 && in_h > 0 && in_w > 0 && in_h <= img_size && in_w <= img_size && out_h > 0 && out_w > 0,
+           "sam_binarize: bad arguments");               // (an input size above img_size would read past the 256 x 256 mask)
+  LL_CHECK((out_h + POST_ROWS - 1) / POST_ROWS < 65536 && n_sel < 65536, "sam_binarize: grid limit");
   LL_LAUNCH_KERNEL(sam_binarize_kernel, dim3((unsigned)((out_w + 255) / 256), (unsigned)((out_h + POST_ROWS - 1) / POST_ROWS), (unsigned)n_sel), dim3(256), 0, (hipStream_t)stream, low, sel, out,
                      img_size, in_h, in_w, out_h, out_w, nested, mask_threshold);
   LL_LAUNCH_CHECK("sam_binarize");
