@@ -208,8 +208,11 @@ typedef struct {
   const void* pad_q; const void* pad_k; const void* pad_v;
 } llmseg_attn_args;
 int llmseg_attn_fwd(const llmseg_attn_args* args, void* stream);
-/* tuning knob (identical results up to fp32 summation order): bit 0 = 1 [default]: SAM 14x14 windows on the resident-window kernel
- * (one workgroup per window and head, no key tiling); 0: the general tiled kernel */
+/* tuning knob, process-global (identical results up to fp32 summation order).  variant & 3 = the kernel of SAM's 14x14 windows (rel_tab_*):
+ * 0 = the general tiled kernel, 1 = the resident-window kernel with register staging (persistent workgroups walk (window, head) items, no
+ * key tiling), 2 [default] = its LDS-DMA form (the only one with the window gather).  At 2, a call that asks for lse takes the tiled kernel and
+ * one whose k_stride_row != v_stride_row the register-staged one.  Bits 4 and up = the cap on the persistent workgroups of the window
+ * kernels (0 = 256, one per CU); an item's arithmetic does not depend on it.  Bits 2-3 are ignored. */
 int llmseg_attn_set_variant(int variant);
 
 /* ---- fused attention backward ----------------------------------------------------------------

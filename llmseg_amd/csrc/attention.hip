@@ -1207,7 +1207,8 @@ int launch_hd(const AttnP& p, hipStream_t s) {
   } else if (HD == 80 && p.gh == 14 && p.gw == 14 && p.Nk == 196 && !p.causal && !p.key_mask)
     LL_LAUNCH_KERNEL((attn_fwd_kernel<HD == 80 ? 80 : HD, HD == 80 ? 3 : 1>), dim3((p.Nq + 127) / 128, p.heads, p.batch), dim3(NT4), 0, s, p);
   else if (p.gw == BKV && (p.Nk % BKV) == 0) {
-    if (HD == 80 && wide && g_attn_glob_dma && (p.Nq % 256) == 0 && p.Nk == p.gh * BKV && (p.gh & 1) == 0 && !p.causal && !p.key_mask && !p.lse && !p.nk_dev)
+    // gh <= 64: the kernel keeps one key-row bias per query and key row in an LDS table of pitch 65 (a taller grid would run into the next query's row)
+    if (HD == 80 && wide && g_attn_glob_dma && (p.Nq % 256) == 0 && p.Nk == p.gh * BKV && (p.gh & 1) == 0 && p.gh <= 64 && !p.causal && !p.key_mask && !p.lse && !p.nk_dev)
       LL_LAUNCH_KERNEL(attn_glob80_dma_kernel, xgrid, dim3(NT8), 0, s, px);
     else if (wide) LL_LAUNCH_KERNEL((attn_fwd_kernel<HD, 2, 8>), xgrid, dim3(NT8), 0, s, px);
     else LL_LAUNCH_KERNEL((attn_fwd_kernel<HD, 2>), grid, dim3(NT4), 0, s, p);
