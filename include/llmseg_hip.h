@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 14
+#define LLMSEG_ABI_VERSION 15
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -296,6 +296,23 @@ int llmseg_act(const void* x, void* y, int64_t n, int32_t act, void* stream);
  * [n_masks][out_h][out_w].  nested = 1: `low` is in the row order the GEMM-form transposed convolutions emit (see head.hip). */
 int llmseg_sam_postprocess(const float* low, float* out, int32_t n_masks, int32_t img_size, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
                            int32_t nested, void* stream);
+/* SAM prompt encoder for point / box / mask prompts (model/segment_anything/modeling/prompt_encoder.py:56-64,78-114,203-238), what
+ * `SamPredictor.predict_torch` runs in front of the mask decoder.  Every stage is fp32; the one rounding is the bf16 store.
+ *   llmseg_sam_dense_prompt: keys bf16 [b][4096][256] = feats bf16 [4096][256] (one image's embedding, channels-last rows) + the dense
+ *     prompt.  mask fp32 [b][65536] low-resolution logits: cell p of prompt i gets feats[p] + mask_downscaling(mask_i)[:, p] (Conv 2x2 s2 ->
+ *     LayerNorm2d(4, eps 1e-6) -> erf GELU -> Conv 2x2 s2 -> LayerNorm2d(16) -> GELU -> Conv 1x1 to 256; the ten tensors bf16 in the
+ *     reference's layouts [4][1][2][2], [4], [4], [4], [16][4][2][2], [16], [16], [16], [256][16], [256]).  nested = 1: `mask` is in the row
+ *     order llmseg_sam_postprocess reads (the mask decoder's own output order), nested = 0: raster 256 x 256.  mask == NULL: keys = feats +
+ *     no_mask bf16 [256] for every prompt, the bits of llmseg_add_rows on the repeated embedding; the ten tensors may then be NULL.
+ *   llmseg_sam_prompt_tokens: out bf16 [b][n + (boxes ? 2 : 1)][256] = PromptEncoder._embed_points / _embed_boxes.  coords fp32 [b][n][2]
+ *     (x, y) in the frame x frame input, labels int32 [b][n] (-1: the not_a_point vector alone, 0 / 1: + point embedding 0 / 1), boxes fp32
+ *     [b][4] XYXY or NULL (NULL: one padding token is appended; else the two corners + point embeddings 2 / 3), gauss fp32 [2][128],
+ *     pe0..pe3 / not_a_point bf16 [256].  n = 0 with boxes is legal.  Nothing is read on the host. */
+int llmseg_sam_dense_prompt(const void* feats, const float* mask, int32_t b, int32_t nested, const void* no_mask, const void* w0, const void* b0,
+                            const void* ln1_w, const void* ln1_b, const void* w3, const void* b3, const void* ln4_w, const void* ln4_b, const void* w6,
+                            const void* b6, void* keys, void* stream);
+int llmseg_sam_prompt_tokens(const float* coords, const int32_t* labels, const float* boxes, int32_t b, int32_t n, int32_t frame, const float* gauss,
+                             const void* pe0, const void* pe1, const void* pe2, const void* pe3, const void* not_a_point, void* out, void* stream);
 /* SAM "everything" mode (model/segment_anything/automatic_mask_generator.py:264-324, utils/amg.py:78-88,156-176,303-346), per candidate
  * mask at the ORIGINAL resolution without materialising the logits there.  low fp32 [n][256*256] (nested as above):
  *   llmseg_sam_mask_stats: stats int32 [n][7] += { |m > thr + off|, |m > thr - off|, |m > thr|, min x, min y, max x, max y } of the

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 14         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 15         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
 NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
@@ -103,6 +103,8 @@ SIGNATURES = {
     "llmseg_swiglu": [_p, _p, _i64, _i64, _i64, _i64, _p],
     "llmseg_act": [_p, _p, _i64, _i32, _p],
     "llmseg_sam_postprocess": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "llmseg_sam_dense_prompt": [_p, _p, _i32, _i32] + [_p] * 13,
+    "llmseg_sam_prompt_tokens": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p],
     "llmseg_sam_mask_stats": [_p, _p, _f32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _p],
     "llmseg_sam_binarize": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _p],
     "llmseg_nms": [_p, _p, _i32, _f32, _p, _p],

@@ -134,7 +134,7 @@ class LISAForCausalLM(TrainableMixin, GenerateMixin, SamDecoderMixin, AmgMixin, 
 
     @classmethod
     def from_pretrained(cls, version, torch_dtype=BF16, device="cuda", dinov2_state=None, lora_r=8, lora_alpha=16, lora_dropout=0.05,
-                        backbone="dinov2", seed=0, new_rows="normal", vocab_size=None, sam_decoder=False, towers=None, **model_args):
+                        backbone="dinov2", seed=0, new_rows="normal", vocab_size=None, sam_decoder=False, towers=None, sam_prompts=False, **model_args):
         """`init_LISA_model` (training.py:139-243) in one call: config.json of the HF LLaVA directory `version` -> model at the tokenizer's
         final vocabulary (`vocab_size` = len(tokenizer) after training.py:130-135 added [SEG] / <im_start> / <im_end>; default: the file's + 1,
         i.e. 32004 for the LLaVA-Lightning v1-1 checkpoints whose 32003 rows already hold the two image tags) -> weights
@@ -142,7 +142,7 @@ class LISAForCausalLM(TrainableMixin, GenerateMixin, SamDecoderMixin, AmgMixin, 
         (`vision_pretrained`, `vision_tower`, `seg_token_idx`, loss weights, ...)."""
         from . import pretrained
         assert torch_dtype == BF16, "the HIP path computes in bf16 (training.py:151-156 `--precision bf16`)"
-        cfg = pretrained.config_from_hf(version, backbone=backbone, sam_decoder=sam_decoder, **(towers or {}))     # towers: {"clip" / "sam" / "dino": config} when not ViT-L / ViT-H / ViT-L
+        cfg = pretrained.config_from_hf(version, backbone=backbone, sam_decoder=sam_decoder, sam_prompts=sam_prompts, **(towers or {}))     # towers: {"clip" / "sam" / "dino": config} when not ViT-L / ViT-H / ViT-L
         file_vocab = cfg.llama.vocab
         if vocab_size is None:
             import warnings

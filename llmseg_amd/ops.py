@@ -385,6 +385,58 @@ def sam_binarize(low, sel, input_size, original_size, img_size=1024, mask_thresh
     return out
 
 
+def sam_dense_prompt(feats, mask, no_mask=None, weights=None, b=None, nested=False, out=None):
+    """The mask decoder's keys in one launch: feats bf16 [4096, 256] + the dense prompt -> bf16 [b * 4096, 256].  mask fp32 [b, 65536] low-resolution
+    logits (nested = the order `sam_decode` returns, else raster 256 x 256) with `weights` = the ten bf16 `mask_downscaling` tensors
+    (0.weight, 0.bias, 1.weight, 1.bias, 3.weight, 3.bias, 4.weight, 4.bias, 6.weight, 6.bias); mask None: + no_mask bf16 [1, 256] for `b` prompts."""
+    _req(feats)
+    assert feats.is_contiguous() and tuple(feats.shape) == (4096, 256)
+    if mask is not None:
+        assert mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous() and mask.dim() == 2 and mask.shape[1] == 65536
+        assert b is None or b == mask.shape[0]
+        b = mask.shape[0]
+        assert weights is not None and len(weights) == 10 and all(w.is_cuda and w.dtype == BF16 and w.is_contiguous() for w in weights)
+        shapes = [(4, 1, 2, 2), (4,), (4,), (4,), (16, 4, 2, 2), (16,), (16,), (16,), (256, 16, 1, 1), (256,)]
+        assert [tuple(w.shape) for w in weights] == shapes, [tuple(w.shape) for w in weights]
+    else:
+        assert b is not None and no_mask is not None
+        _req(no_mask)
+        assert no_mask.is_contiguous() and no_mask.numel() == 256
+        weights = [None] * 10
+    if out is None:
+        out = torch.empty((b * 4096, 256), device=feats.device, dtype=BF16)
+    assert out.dtype == BF16 and out.is_contiguous() and out.numel() == b * 4096 * 256
+    _lib.check(_lib.load().llmseg_sam_dense_prompt(_ptr(feats), _ptr(mask), b, 1 if nested else 0, _ptr(no_mask), *[_ptr(w) for w in weights], _ptr(out),
+                                                   _stream()), "sam_dense_prompt")
+    return out
+
+
+def sam_prompt_tokens(coords, labels, boxes, gauss, point_embeddings, not_a_point, frame=1024, b=None, out=None):
+    """`PromptEncoder._embed_points` / `_embed_boxes` in one launch: coords fp32 [b, n, 2] (x, y) in the input frame, labels int32 [b, n] in {-1, 0, 1}
+    (both None: no points), boxes fp32 [b, 4] XYXY or None, gauss fp32 [2, 128], point_embeddings = four bf16 [1, 256], not_a_point bf16 [1, 256]
+    -> bf16 [b, n + (2 if boxes is not None else 1), 256].  Nothing is read back on the host."""
+    n = 0
+    if coords is not None:
+        assert coords.is_cuda and coords.dtype == torch.float32 and coords.is_contiguous() and coords.dim() == 3 and coords.shape[2] == 2
+        assert labels is not None and labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == tuple(coords.shape[:2])
+        b, n = int(coords.shape[0]), int(coords.shape[1])
+    if boxes is not None:
+        assert boxes.is_cuda and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 2 and boxes.shape[1] == 4
+        assert b is None or b == boxes.shape[0]
+        b = int(boxes.shape[0])
+    assert b is not None and (n > 0 or boxes is not None), "no points and no boxes"
+    assert gauss.is_cuda and gauss.dtype == torch.float32 and gauss.is_contiguous() and tuple(gauss.shape) == (2, 128)
+    emb = list(point_embeddings) + [not_a_point]
+    assert len(emb) == 5 and all(e.is_cuda and e.dtype == BF16 and e.is_contiguous() and e.numel() == 256 for e in emb)
+    T = n + (2 if boxes is not None else 1)
+    if out is None:
+        out = torch.empty((b, T, 256), device=gauss.device, dtype=BF16)
+    assert out.dtype == BF16 and out.is_contiguous() and out.numel() == b * T * 256
+    _lib.check(_lib.load().llmseg_sam_prompt_tokens(_ptr(coords) if n else None, _ptr(labels) if n else None, _ptr(boxes), b, n, int(frame), _ptr(gauss),
+                                                    *[_ptr(e) for e in emb], _ptr(out), _stream()), "sam_prompt_tokens")
+    return out
+
+
 RESAMPLE = {"bilinear": 0, "bicubic": 1}        # LLMSEG_RESAMPLE_* of include/llmseg_hip.h
 
 

@@ -73,10 +73,19 @@ class LisaConfig:
     regression_loss_weight: float = 1.0
     build_unused_towers: bool = True   # keep both vision backbones' parameters, as the reference does
     sam_decoder: bool = False          # SAM prompt encoder (text path) + mask decoder: only `evaluate()` reaches them (LISA.py:523-557)
+    sam_prompts: bool = False          # + the prompt encoder's mask_downscaling stack (`SamPredictor` mask prompts); needs sam_decoder=True
+
+    def __post_init__(self):
+        check_sam_prompts(self)
 
     @property
     def n_img_tokens(self):
         return (self.clip.img // self.clip.patch) ** 2
+
+
+def check_sam_prompts(c):
+    if c.sam_prompts and not c.sam_decoder:
+        raise ValueError("LisaConfig(sam_prompts=True) needs sam_decoder=True: the dense prompt feeds the mask decoder and nothing else")
 
 
 def llama_shapes(c, pfx="model."):
@@ -220,6 +229,20 @@ def sam_decoder_shapes(pfx="model.visual_model.", D=256, mlp=2048):
     return s
 
 
+def sam_prompt_shapes(pfx="model.visual_model.", D=256, mask_in_chans=16):
+    """The prompt encoder's dense (mask) path, `mask_downscaling` (prompt_encoder.py:56-64; mask_in_chans = 16, build_sam.py:73): Conv2d(1, 4, 2, 2),
+    LayerNorm2d(4), GELU, Conv2d(4, 16, 2, 2), LayerNorm2d(16), GELU, Conv2d(16, D, 1).  Kept apart from `sam_decoder_shapes`: only
+    `LisaConfig(sam_prompts=True)` allocates and loads these."""
+    m, C4, C = pfx + "prompt_encoder.mask_downscaling.", mask_in_chans // 4, mask_in_chans
+    s = {}
+    s[m + "0.weight"], s[m + "0.bias"] = (C4, 1, 2, 2), (C4,)
+    s[m + "1.weight"], s[m + "1.bias"] = (C4,), (C4,)
+    s[m + "3.weight"], s[m + "3.bias"] = (C, C4, 2, 2), (C,)
+    s[m + "4.weight"], s[m + "4.bias"] = (C,), (C,)
+    s[m + "6.weight"], s[m + "6.bias"] = (D, C, 1, 1), (D,)
+    return s
+
+
 def lisa_shapes(c: LisaConfig):
     s = {}
     s.update(llama_shapes(c.llama))
@@ -232,6 +255,9 @@ def lisa_shapes(c: LisaConfig):
     s.update(head_shapes(c.llama.hidden, c.out_dim, c.dino.dim))
     if c.sam_decoder:
         s.update(sam_decoder_shapes())
+    check_sam_prompts(c)                  # the flag may have been set after construction
+    if c.sam_prompts:
+        s.update(sam_prompt_shapes())
     return s
 
 
@@ -310,7 +336,8 @@ def init_random_(tree: ParamTree, shapes, seed=0):
     for name, shp in shapes.items():
         t = tree[name]
         last = name.rsplit(".", 1)[-1]
-        is_norm = ("norm" in name or ".neck.1." in name or ".neck.3." in name or last == "gamma")
+        is_norm = ("norm" in name or ".neck.1." in name or ".neck.3." in name or last == "gamma" or ".mask_downscaling.1." in name
+                   or ".mask_downscaling.4." in name)
         if is_norm and last in ("weight", "gamma"):
             t.copy_(1.0 + 0.1 * torch.randn(shp, device=dev, generator=gen))
         elif last == "bias":

@@ -73,6 +73,18 @@ class SamDecoderMixin:
         d["samdec"] = s
         return s
 
+    def predictor(self, **kw):
+        """`SamPredictor(model)` (llmseg_amd/predictor.py): point, box and mask prompts on one image embedding."""
+        from .predictor import SamPredictor
+        return SamPredictor(self, **kw)
+
+    def mask_downscaling_weights(self):
+        """The ten tensors of prompt_encoder.mask_downscaling in `ops.sam_dense_prompt`'s order."""
+        P, md = self.params, PFX + "prompt_encoder.mask_downscaling."
+        if md + "0.weight" not in P.flat:
+            raise ValueError("mask_input needs the prompt encoder's mask_downscaling tensors: construct the model with LisaConfig(sam_decoder=True, sam_prompts=True)")
+        return [P[f"{md}{i}.{n}"] for i in (0, 1, 3, 4, 6) for n in ("weight", "bias")]
+
     def _sd_attn(self, p, q_in, k_in, v_in, b, nq, nk, padded):
         """transformer.py:185-245 on row matrices: q_in [b*nq, 256], k_in / v_in [b*nk, 256] -> out_proj(attention) [b*nq, 256]."""
         P, S = self.params, self._samdec()
@@ -94,11 +106,13 @@ class SamDecoderMixin:
         return o, wo, P[p + "out_proj.bias"]
 
     @torch.no_grad()
-    def sam_decode(self, feats_cl, text_embeds, sparse=None, multimask_output=False):
+    def sam_decode(self, feats_cl, text_embeds, sparse=None, multimask_output=False, mask_input=None, mask_nested=False):
         """feats_cl bf16 [4096, 256]: one image's SAM embedding, channels-last rows; text_embeds bf16 [b, 256]: its [SEG] embeddings
         (or `sparse` bf16 [b, n, 256]: any sparse prompt tokens, e.g. `embed_points`).
         -> (low_res fp32 [b, 65536] mask logits in nested row order, iou bf16 [b, 1]); with multimask_output (mask tokens 1..3,
-        mask_decoder.py:97-104): low_res [b, 3, 65536], iou [b, 3]."""
+        mask_decoder.py:97-104): low_res [b, 3, 65536], iou [b, 3].
+        mask_input fp32 [b, 65536]: the dense (mask) prompt, low-resolution logits in raster order or -- mask_nested -- in the order this function
+        returns them; the keys then come from `ops.sam_dense_prompt` (needs `LisaConfig(sam_prompts=True)`).  None: no_mask_embed, as before."""
         P, S = self.params, self._samdec()
         if sparse is None:
             sparse = text_embeds.to(BF16)[:, None, :]
@@ -108,7 +122,13 @@ class SamDecoderMixin:
         t = m + "transformer."
         ln = lambda x, name, eps=1e-5: ops.norm(x, P[name + ".weight"], P[name + ".bias"], eps=eps, rms=False)
         pe_q = torch.cat([S["out_tokens"][None].expand(b, -1, -1), sparse.to(BF16)], 1).reshape(b * NT, D).contiguous()   # point_embedding
-        keys = ops.add_rows(feats_cl.repeat(b, 1) if b > 1 else feats_cl.contiguous(), P[PFX + "prompt_encoder.no_mask_embed.weight"])   # + dense prompt
+        if mask_input is None:
+            keys = ops.add_rows(feats_cl.repeat(b, 1) if b > 1 else feats_cl.contiguous(), P[PFX + "prompt_encoder.no_mask_embed.weight"])   # + dense prompt
+        else:
+            if tuple(mask_input.shape) != (b, 65536):
+                raise ValueError(f"mask_input must be [{b}, 65536] (one low-resolution mask per prompt), got {tuple(mask_input.shape)}")
+            keys = ops.sam_dense_prompt(feats_cl.contiguous(), mask_input.to(self.device_, torch.float32).contiguous(), weights=self.mask_downscaling_weights(),
+                                        nested=mask_nested)
         queries = pe_q
         for i in range(2):
             p = f"{t}layers.{i}."
