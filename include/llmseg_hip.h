@@ -465,7 +465,8 @@ int llmseg_union_resize_iou(const uint8_t* segs, const uint8_t* select, const ui
 /* ---- proposal decode + training targets on the device (the reference does this per sample on CPU workers) -----
  * rle_decode: COCO run-length proposals -> dense uint8 masks (pycocotools `mask_util.decode`, utils/sam_mask_reader.py:86-87).  run_ends =
  *   inclusive prefix sums of every mask's run lengths, concatenated; offsets int64 [K+1] delimits mask k's slice; runs alternate 0 / 1 from 0
- *   and walk the image column-major.  out uint8 [K][H][W] (hwk = 0) or [H][W][K] (hwk = 1, the reader's layout).
+ *   and walk the image column-major.  out uint8 [K][H][W] (hwk = 0) or [H][W][K] (hwk = 1, the reader's layout).  Pixels beyond the last run of a
+ *   run list that ends before H W (malformed input) are 0, after an even or an odd number of runs.
  * mask_targets: `compute_all_iou` / `compute_all_iop` (utils/utils.py:234-272) for all K proposals: ground truth gt [Hg][Wg] resampled to the
  *   proposals' H x W grid through the nearest-neighbour index maps gy [H], gx [W] (skimage.transform.resize(order=0) rule, built on the host
  *   in float64), counts int64 [K][2] += {|seg & gt|, |seg|}, gt_area int64 [1] += |gt'| (caller zero-fills both), then

@@ -718,7 +718,7 @@ __global__ __launch_bounds__(256) void union_resize_iou_kernel(const uint8_t* __
     if (t == ignore) continue;
     const uint8_t* px = segs + ((long)sy * W + sx) * K;
     int p = 0;
-    for (int k = 0; k < K; ++k) p |= (sel[k] & (px[k] != 0));
+    for (int k = 0; k < K; ++k) p |= ((sel[k] != 0) & (px[k] != 0));      // any non-zero select byte selects (2, 255, ...), not only odd ones
     c[2 + p]++;
     if (p == t) c[p]++;
     if (t < 2) c[4 + t]++;

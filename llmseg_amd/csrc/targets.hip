@@ -23,12 +23,12 @@ __global__ __launch_bounds__(256) void rle_decode_kernel(const uint32_t* __restr
     else { x = (int)(i % W); const long r = i / W; y = (int)(r % H); k = (int)(r / H); }
     const uint32_t p = (uint32_t)x * (uint32_t)H + (uint32_t)y;
     long lo = offs[k], hi = offs[k + 1];                 // first run whose end exceeds p
-    const long base = lo;
+    const long base = lo, last = hi;
     while (lo < hi) {
       const long mid = (lo + hi) >> 1;
       if (ends[mid] > p) hi = mid; else lo = mid + 1;
     }
-    out[i] = (uint8_t)((lo - base) & 1);                 // beyond the last run (malformed input): parity of the run count, as pycocotools leaves zeros
+    out[i] = lo == last ? (uint8_t)0 : (uint8_t)((lo - base) & 1);      // beyond the last run (malformed input): zero after any number of runs, as pycocotools leaves it
   }
 }
 
