@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 15
+#define LLMSEG_ABI_VERSION 16
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -165,6 +165,33 @@ typedef struct {
   int32_t out_f32; int32_t reserved1;
 } llmseg_gemm_w8_args;
 int llmseg_gemm_w8(const llmseg_gemm_w8_args* args, void* stream);
+
+/* ---- sampling (generate(do_sample=True)): temperature, top-k, top-p, the draw, the eos rule: ONE launch ----
+ * Per row n of logits [N][ldl] bf16, with temperature T > 0, top_k k >= 0 (0 = off), top_p p in (0, 1] (1 = off) and a uniform u[n] in [0, 1),
+ * in Hugging Face's order (temperature, top-k, top-p, draw), stated in exact arithmetic:
+ *   1. z_i = l_i / T.
+ *   2. K1 = { i : z_i >= the k-th largest z } when 1 <= k < V (ties at the k-th value are ALL kept), every index otherwise; -inf is never
+ *      kept while a larger logit exists.
+ *   3. q = softmax of z over K1.
+ *   4. p < 1: m_i = sum of q_j over { j in K1 : q_j <= q_i };  K2 = { i in K1 : m_i > 1 - p }.  p = 1: K2 = K1.  A group of equal logits is
+ *      kept or dropped AS A WHOLE; the top group has m = 1 and is always kept (min_tokens_to_keep = 1).  (TopPLogitsWarper splits a tie group
+ *      that straddles the boundary by torch.sort's unspecified order; this rule keeps the whole group, so its kept set is a superset whose
+ *      extra members all have the smallest kept logit.)
+ *   5. r_i = q_i / sum_{K2} q.  next[n] = the smallest i in K2, in TOKEN-ID order, with sum_{j in K2, j <= i} r_j > u[n]; the largest index of
+ *      K2 if rounding leaves none.  logprob[n] = ln r_next.
+ * Then the greedy loop's eos rule, when eos >= 0: a row with unfinished[n] == 0 emits `pad` (logprob 0), and unfinished[n] &= (next[n] != eos);
+ * unfinished == NULL: every row is unfinished.  eos < 0: no eos rule, `unfinished` is not touched.
+ * Optional outputs (NULL = not written): logprob fp32 [N]; kept int32 [N] = |K2|; probs fp32 [N][ldp] = r, zeros outside K2.
+ * Arithmetic: a token's weight is e = expf((l - l_max) / T) in fp32, held as the integer floor(e * 2^40) (2^(62 - bits(V)) above V = 2^22);
+ * every sum (per-bin mass of the two-level histogram selects on the order-preserving 16-bit key, the softmax denominator, the CDF) is an
+ * INTEGER sum and every threshold ((1 - p) S, u S2: formed once in fp64, floored) an integer compare: no floating-point atomics and no
+ * order-dependent sum, so the result is a pure function of (logits, T, k, p, u).  One workgroup per row; V <= 32768 reads the row once into
+ * registers, larger V re-reads it per pass.  next[n] is always in [0, V) (or `pad`); a row with a NaN or without a finite logit gives an
+ * unspecified token of that range.  Checked before the launch: pointers and their alignment, 1 <= N, V < 2^31, ldl >= V, ldp >= V, T finite
+ * and > 0, k >= 0, 0 < p <= 1. */
+int llmseg_sample_tokens(const void* logits, int64_t ldl, int64_t N, int64_t V, float temperature, int32_t top_k, float top_p, const float* u,
+                         int64_t eos, int64_t pad, int64_t* unfinished /* nullable, in/out */, int64_t* next, float* logprob /* nullable */,
+                         int32_t* kept /* nullable */, float* probs /* nullable */, int64_t ldp, void* stream);
 
 /* ---- fused attention forward -----------------------------------------------------------------
  * O[b][h][q][:] = softmax_k( scale * Q.K^T + bias + mask ) V, online softmax in fp32, bf16 MFMA.

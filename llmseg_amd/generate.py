@@ -16,6 +16,8 @@ MI355X-first shape of the loop:
 HF greedy-search rules restated from `transformers==4.29.0 generation/utils.py::greedy_search` (third party): finished rows emit
 `pad_token_id`, a row finishes on `eos_token_id`, the loop stops when all rows are finished or `max_new_tokens` tokens were added.
 """
+import math
+
 import torch
 
 from . import ops
@@ -279,8 +281,9 @@ class GenerateMixin:
 
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
-                 weight_bits=None, attention_mask=None):
-        """Greedy generation.  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
+                 weight_bits=None, attention_mask=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None,
+                 return_logprobs=False):
+        """Greedy generation (or sampling: do_sample, below).  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
         IMAGE_TOKEN_INDEX each.
         -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
         attention_mask (bool [N, L], None = every token is a prompt token): prompts of different lengths, RIGHT-padded (`pad_prompts` builds
@@ -296,7 +299,32 @@ class GenerateMixin:
         (`ops.gemm_w8`): half the bytes of a step.  The weights are re-quantised at every call (`w8_prepare_ms()` gives the cost);
         `decode_weights_i8()` returns them.  Measured at Llama-7B (profiles/w8_decode.md): 2.70 / 2.85 / 3.40 / 4.97 ms per token at 1 / 2 / 4 / 8 sequences
         against 3.33 / 3.88 / 4.33 / 5.08 in bf16 -- at 8 sequences there is no gain (the int8 kernel takes as long as the bf16 kernel there, whatever
-        the FMA form) -- and 9.4 ms per call for the merge + quantisation, repaid after about 11 tokens at one sequence."""
+        the FMA form) -- and 9.4 ms per call for the merge + quantisation, repaid after about 11 tokens at one sequence.
+        do_sample=True: every token is drawn by `ops.sample_tokens` (ONE launch per step: temperature, top-k, top-p, the draw and the eos / pad
+        bookkeeping; the rule is stated in include/llmseg_hip.h) instead of the arg-max; everything before the pick -- prefill, decode step,
+        hipGraph, weight_bits, attention_mask -- is the greedy route's.  temperature > 0; top_k >= 0 with 0 = OFF (Hugging Face's default is 50:
+        pass top_k=50 for its behaviour); 0 < top_p <= 1 with 1 = off.  Ties are kept or dropped as whole groups (HF's TopPLogitsWarper splits a
+        group that straddles the top-p boundary by sort order).  The uniforms are one fp32 tensor [N, max_new_tokens] in [0, 1): drawn once before
+        the loop from `torch.Generator(device).manual_seed(seed)` (seed=None: torch's global generator), or given as `uniforms=` (not both); step
+        s of row n consumes uniforms[n, s], so a call is a pure function of (weights, prompt, arguments, uniforms).  With do_sample=False the
+        sampling arguments must stay at their defaults.  return_logprobs=True (sampling only) adds a third result: fp32 [N, n_new], ln of the
+        renormalised probability each token was drawn with (0 where a finished row emitted pad_token_id)."""
+        defaults = temperature == 1.0 and top_k == 0 and top_p == 1.0 and seed is None and uniforms is None and not return_logprobs
+        if not do_sample and not defaults:
+            raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True (greedy decoding takes none of them)")
+        if do_sample:
+            if not (isinstance(temperature, (int, float)) and math.isfinite(temperature) and temperature > 0):
+                raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+            if not (isinstance(top_k, int) and not isinstance(top_k, bool) and 0 <= top_k < 2 ** 31):
+                raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k!r}")
+            if not (isinstance(top_p, (int, float)) and 0 < top_p <= 1):
+                raise ValueError(f"top_p must be in (0, 1] (1 = off), got {top_p!r}")
+            if seed is not None and uniforms is not None:
+                raise ValueError("pass seed= or uniforms=, not both")
+            if uniforms is not None and (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or
+                                         tuple(uniforms.shape) != (input_ids.shape[0], max_new_tokens)):
+                raise ValueError(f"uniforms must be an fp32 tensor [N, max_new_tokens] = {(input_ids.shape[0], max_new_tokens)}, got "
+                                 f"{getattr(uniforms, 'dtype', type(uniforms))} {tuple(getattr(uniforms, 'shape', ()))}")
         if weight_bits not in (None, 8):
             raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
         if weight_bits == 8 and not fuse_decode:
@@ -365,14 +393,27 @@ class GenerateMixin:
         seqs = [input_ids.to(dev)]
         unfinished = torch.ones((N,), dtype=torch.int64, device=dev)
         n_new = 0
+        if do_sample:
+            if uniforms is None:
+                gen = None if seed is None else torch.Generator(device=dev).manual_seed(int(seed))
+                uniforms = torch.rand((N, max_new_tokens), device=dev, dtype=torch.float32, generator=gen)
+            u_steps = uniforms.to(dev).t().contiguous()        # [max_new_tokens, N]: step s reads one contiguous row
+            lps = []
         while True:
-            nxt = logits.float().argmax(-1)
-            if eos_token_id is not None:
-                nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
+            if do_sample:                                      # one launch: the pick, pad for finished rows and the update of `unfinished`
+                nxt, lp, _, _ = ops.sample_tokens(logits, temperature, top_k, top_p, u_steps[n_new], eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                                                  unfinished=unfinished, want_logprob=return_logprobs)
+                if return_logprobs:
+                    lps.append(lp[:, None])
+            else:
+                nxt = logits.float().argmax(-1)
+                if eos_token_id is not None:
+                    nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
             seqs.append(nxt[:, None])
             n_new += 1
             if eos_token_id is not None:
-                unfinished = unfinished * (nxt != eos_token_id).long()
+                if not do_sample:
+                    unfinished = unfinished * (nxt != eos_token_id).long()
                 if int(unfinished.max()) == 0:                 # the one host synchronisation of a step (HF's loop has the same)
                     break
             if n_new == max_new_tokens:
@@ -387,8 +428,10 @@ class GenerateMixin:
         if ragged:                                             # row i: prompt, new tokens, fill
             out = torch.cat([seqs[0], torch.full((N, n_new), fill, dtype=torch.int64, device=dev)], 1)
             out.scatter_(1, lens.to(dev)[:, None] + torch.arange(n_new, device=dev)[None, :], torch.cat(seqs[1:], 1))
-            return out, hidden[:, :T + n_new - 1]
-        return torch.cat(seqs, 1), hidden[:, :T + n_new - 1]
+            res = (out, hidden[:, :T + n_new - 1])
+        else:
+            res = (torch.cat(seqs, 1), hidden[:, :T + n_new - 1])
+        return res + (torch.cat(lps, 1),) if return_logprobs else res
 
     @staticmethod
     def _ragged_prompts(input_ids, attention_mask):

@@ -207,6 +207,38 @@ def gemm_w8(a, q, scale, residual=None, out=None, out_f32=False):
     return out
 
 
+def sample_tokens(logits, temperature, top_k, top_p, u, eos_token_id=None, pad_token_id=0, unfinished=None, want_logprob=False, want_kept=False,
+                  want_probs=False, next=None, logprob=None, kept=None, probs=None):
+    """One token per row of logits [N, V] bf16 (rows may be strided) by the rule of include/llmseg_hip.h (`llmseg_sample_tokens`): temperature > 0,
+    top_k >= 0 (0 = off), 0 < top_p <= 1 (1 = off), u fp32 [N] uniforms in [0, 1) -- one launch, a pure function of its inputs.
+    eos_token_id (None = no eos rule): a row with unfinished[n] == 0 gets pad_token_id, then unfinished &= (token != eos); `unfinished` (int64 [N])
+    is updated IN PLACE.  -> (next int64 [N], logprob fp32 [N] | None, kept int32 [N] | None, probs fp32 [N, V] | None): the optional outputs are
+    written when asked for (want_*) or when a buffer is passed (probs may be a strided view)."""
+    _req(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    N, V = logits.shape
+    dev = logits.device
+    assert u.is_cuda and u.dtype == torch.float32 and u.shape == (N,) and u.is_contiguous()
+    if next is None:
+        next = torch.empty((N,), device=dev, dtype=torch.int64)
+    if logprob is None and want_logprob:
+        logprob = torch.empty((N,), device=dev, dtype=torch.float32)
+    if kept is None and want_kept:
+        kept = torch.empty((N,), device=dev, dtype=torch.int32)
+    if probs is None and want_probs:
+        probs = torch.empty((N, V), device=dev, dtype=torch.float32)
+    assert next.is_cuda and next.dtype == torch.int64 and next.shape == (N,) and next.is_contiguous()
+    assert unfinished is None or (unfinished.is_cuda and unfinished.dtype == torch.int64 and unfinished.shape == (N,) and unfinished.is_contiguous())
+    assert logprob is None or (logprob.is_cuda and logprob.dtype == torch.float32 and logprob.shape == (N,) and logprob.is_contiguous())
+    assert kept is None or (kept.is_cuda and kept.dtype == torch.int32 and kept.shape == (N,) and kept.is_contiguous())
+    assert probs is None or (probs.is_cuda and probs.dtype == torch.float32 and probs.shape == (N, V) and probs.stride(1) == 1)
+    _lib.check(_lib.load().llmseg_sample_tokens(_ptr(logits), max(logits.stride(0), V) if N == 1 else logits.stride(0), N, V, float(temperature), int(top_k), float(top_p), _ptr(u),
+                                                -1 if eos_token_id is None else int(eos_token_id), 0 if pad_token_id is None else int(pad_token_id),
+                                                _ptr(unfinished), _ptr(next), _ptr(logprob), _ptr(kept), _ptr(probs),
+                                                0 if probs is None else max(probs.stride(0), V) if N == 1 else probs.stride(0), _stream()), "sample_tokens")
+    return next, logprob, kept, probs
+
+
 def gemm_batched(a, w, out, M, N, K, lda, ldw, ldc, batch, sA, sW, sC, out_f32=True, alpha=1.0, trans_a=False, trans_w=False,
                  batch2=1, sA2=0, sW2=0, sC2=0):
     """Strided-batched GEMM on raw strides (elements); used for the per-head q.R^T relative-position products."""
