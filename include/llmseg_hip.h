@@ -31,10 +31,10 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * an entry point whose struct does not have exactly that size returns LLMSEG_EINVAL ("ABI mismatch") before reading any other field,
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
- * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args, 5 = llmseg_lora_down_args; -1 for an unknown index) so a binding can assert at load time;
+ * llmseg_version() is bumped whenever a struct or a signature changes (17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 16
+#define LLMSEG_ABI_VERSION 17
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -122,7 +122,7 @@ typedef struct {
    * dl_ldo); the call also writes dl_out[b][h][q] = sum_d dO * O (fp32 [batch][dl_heads][dl_T]) -- llmseg_attn_bwd's `delta`, which can then be passed with
    * delta_ready = 1.  In the reduce launch of a K-sliced product, by the attention backward's delta kernel behind the product otherwise; same bits.  NULL = off. */
   const void* dl_o; int64_t dl_ldo; float* dl_out; int32_t dl_heads; int32_t dl_T;
-  /* with nb_lora_t (ABI 8): the LoRA operand still as the K-slice partials llmseg_lora_down_parts left (fp32 [nb_lora_S][M][16]); the tail adds them in order, scales by
+  /* with nb_lora_t (ABI 8): the LoRA operand still as the K-slice partials llmseg_lora_down left on request (llmseg_lora_down_args.parts_S;fp32 [nb_lora_S][M][16]); the tail adds them in order, scales by
    * nb_lora_scale, rounds to bf16 (llmseg_lora_down's finish arithmetic), uses the result AND stores it to nb_lora_t[:, 0:16] (+ nb_lora_zero zero columns) for
    * llmseg_lora_wgrads: the finish launch of the backward's rank-8 down projection rides in the reduce launch.  NULL = nb_lora_t is an input. */
   const float* nb_lora_part; int32_t nb_lora_S; float nb_lora_scale; int32_t nb_lora_zero; int32_t reserved3;
@@ -604,12 +604,42 @@ typedef struct {
   uint32_t seg_rows;           /* 0 = one segment (all rows at rng_state[1]) */
   uint32_t reserved0;          /* 0 */
 } llmseg_dropout;
-int llmseg_lora_down(const void* x0, const void* x1, int64_t ldx, const void* w0, const void* w1, void* y, int64_t ldy, int64_t M, int64_t K,
-                     int32_t w_kr, float alpha, int32_t zero_cols, const llmseg_dropout* drop, void* stream);
-/* lora_down with caller-owned scratch (fp32, >= 2 * 32 * M * 16 * 4 bytes lets every split be taken): short activations (M = 2 x 319) are
- * split along K over several workgroups per 16-row tile so that the whole chip fetches the operand, a second launch adds the slices */
-int llmseg_lora_down_ws(const void* x0, const void* x1, int64_t ldx, const void* w0, const void* w1, void* y, int64_t ldy, int64_t M, int64_t K,
-                        int32_t w_kr, float alpha, int32_t zero_cols, const llmseg_dropout* drop, void* scratch, int64_t scratch_bytes, void* stream);
+/* lora_down (ABI 17: one entry point with a sized argument struct; it replaces llmseg_lora_down_ws / _parts / _pack). */
+typedef struct {
+  uint32_t struct_size;  /* = sizeof(llmseg_lora_down_args) (ABI guard) */
+  uint32_t reserved0;    /* 0 */
+  const void* x0;        /* [M][K] at row pitch ldx */
+  const void* x1;        /* second branch (with w1), or NULL: one branch; may equal x0 (one load feeds both, each with its own dropout stream) */
+  int64_t ldx;
+  const void* w0;        /* [8][K], or [K][8] when w_kr */
+  const void* w1;
+  void* y;               /* [M][8 nb + zero_cols] at row pitch ldy */
+  int64_t ldy;
+  int64_t M, K;
+  int32_t w_kr;
+  float alpha;
+  int32_t zero_cols;     /* multiple of 8, <= 480 */
+  int32_t reserved1;     /* 0 */
+  const llmseg_dropout* drop;
+  /* caller-owned scratch (fp32; NULL = none; >= 2 * 32 * M * 16 * 4 bytes lets every split be taken): short activations (M = 2 x 319) are split along K over
+   * several workgroups per 16-row tile so that the whole chip fetches the operand, and a second launch (the finish) adds the slices in order */
+  void* scratch;
+  int64_t scratch_bytes;
+  /* both set or both NULL.  Set: a K-sliced product is left UNFINISHED: *parts_S = slice count with the fp32 partials [S][M][16] in `scratch` and y untouched
+   * (hand them to llmseg_gemm_args.nb_lora_part), or 0 when the shape took no slices and y is complete; *parts_scale = alpha * dropout scale (the finish
+   * factor), written on every successful call. */
+  int32_t* parts_S;
+  float* parts_scale;
+  /* pack_aq != NULL: llmseg_lora_pack(pack_aq, ..., pack_s) of the same layer in the same call.  The two are independent (activations vs. weights): where the
+   * down projection runs as K slices the pack rides in its finish launch -- one launch fewer per LoRA'd projection -- else it is one more launch; the same
+   * bits as the two calls.  Not together with parts_S (LLMSEG_EINVAL, nothing launched). */
+  const void *pack_aq, *pack_bq, *pack_av, *pack_bv;
+  void *pack_w2b, *pack_w2a, *pack_bt;
+  int64_t pack_H;
+  float pack_s;
+  int32_t reserved2;     /* 0 */
+} llmseg_lora_down_args;
+int llmseg_lora_down(const llmseg_lora_down_args* args, void* stream);
 /* workspace: row slices x nz (1 or 2 products) x 8 N floats of partials (NULL, or room for fewer than two slices: one slice, no fold launch).
  * The dispatch takes max(1, 256 / (ceil(N / 64) * nz), min(32, M / 512)) slices -- 256 for N = 8 with one product -- cut to what the
  * workspace holds; slices * nz * 8 N * 4 bytes lets every slice be taken (at most 256 * 8 * 64 * 4 = 512 KiB below M = 1024, 32 slices above). */
@@ -626,16 +656,6 @@ int llmseg_lora_wgrads(const void* dq, const void* dv, int64_t ldd, const void* 
 int llmseg_lora_apply(void* y, int64_t ldy, const void* xa, int64_t ldxa, const void* w0, const void* w1, int64_t M, int64_t N, int32_t w_rn,
                       float alpha, const llmseg_dropout* drop, void* stream);
 int llmseg_lora_pack(const void* aq, const void* bq, const void* av, const void* bv, void* w2b, void* w2a, void* bt, int64_t H, float s, void* stream);
-/* llmseg_lora_down_ws that leaves a K-sliced product UNFINISHED (ABI 8): *S_out = slice count with the fp32 partials [S][M][16] in `scratch` and y untouched (hand them
- * to llmseg_gemm_args.nb_lora_part), or 0 when the shape took no slices and y is complete; *scale_out = alpha * dropout scale (the finish factor). */
-int llmseg_lora_down_parts(const void* x0, const void* x1, int64_t ldx, const void* w0, const void* w1, void* y, int64_t ldy, int64_t M, int64_t K,
-                           int32_t w_kr, float alpha, int32_t zero_cols, const llmseg_dropout* drop, void* scratch, int64_t scratch_bytes, int32_t* S_out,
-                           float* scale_out, void* stream);
-/* llmseg_lora_down_ws followed by llmseg_lora_pack in one call (ABI 8): the two are independent (activations vs. weights), so where the down projection runs
- * as K slices the pack rides in its finish launch -- one launch fewer per LoRA'd projection; the same bits as the two calls. */
-int llmseg_lora_down_pack(const void* x0, const void* x1, int64_t ldx, const void* w0, const void* w1, void* y, int64_t ldy, int64_t M, int64_t K,
-                          int32_t w_kr, float alpha, int32_t zero_cols, const llmseg_dropout* drop, void* scratch, int64_t scratch_bytes, const void* aq,
-                          const void* bq, const void* av, const void* bv, void* w2b, void* w2a, void* bt, int64_t H, float s, void* stream);
 /* out[c][r] = in[r][c] (bf16; in [rows][cols] with leading dimension ld_in, out [cols][ld_out]); rows r in [rows, rows_pad) of the
  * source are taken as zero.  Lets the weight / input gradients of a wide trainable Linear (lm_head: dX = dY.W, dW = dY^T.X) run on
  * the K-contiguous LDS-DMA GEMM kernels with the contraction dimension padded to a multiple of 64. */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 16         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 17         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
 NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
@@ -81,6 +81,15 @@ class Dropout(C.Structure):
 
 _i64, _i32, _f32, _p = C.c_int64, C.c_int32, C.c_float, C.c_void_p
 _dp = C.POINTER(Dropout)
+
+
+class LoraDownArgs(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("x0", _p), ("x1", _p), ("ldx", _i64), ("w0", _p), ("w1", _p), ("y", _p), ("ldy", _i64),
+                ("M", _i64), ("K", _i64), ("w_kr", _i32), ("alpha", _f32), ("zero_cols", _i32), ("reserved1", _i32), ("drop", _dp),
+                ("scratch", _p), ("scratch_bytes", _i64), ("parts_S", C.POINTER(C.c_int32)), ("parts_scale", C.POINTER(C.c_float)),
+                ("pack_aq", _p), ("pack_bq", _p), ("pack_av", _p), ("pack_bv", _p), ("pack_w2b", _p), ("pack_w2a", _p), ("pack_bt", _p),
+                ("pack_H", _i64), ("pack_s", _f32), ("reserved2", _i32)]
+
 
 # name -> argtypes (restype is int unless noted); must list EVERY symbol of include/llmseg_hip.h
 SIGNATURES = {
@@ -157,14 +166,11 @@ SIGNATURES = {
     "llmseg_attn_ds": [_p, _p, _p, _i64, _i32, _i32, _f32, _p],
     "llmseg_ce_bwd": [_p, _p, _p, _p, _i32, _i32, _i64, _i64, _p],
     "llmseg_scatter_add_rows": [_p, _p, _p, _i64, _i64, _p],
-    "llmseg_lora_down": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _i32, _dp, _p],
-    "llmseg_lora_down_ws": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _i32, _dp, _p, _i64, _p],
+    "llmseg_lora_down": [C.POINTER(LoraDownArgs), _p],
     "llmseg_lora_outer": [_p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _i64, _i32, _f32, _dp, _p, _i64, _p],
     "llmseg_lora_wgrads": [_p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _f32, _dp, _p, _i64, _p],
     "llmseg_lora_apply": [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _i32, _f32, _dp, _p],
     "llmseg_lora_pack": [_p, _p, _p, _p, _p, _p, _p, _i64, _f32, _p],
-    "llmseg_lora_down_parts": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _i32, _dp, _p, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_float), _p],
-    "llmseg_lora_down_pack": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _i32, _dp, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _f32, _p],
     "llmseg_transpose_pad": [_p, _p, _i64, _i64, _i64, _i64, _i64, _p],
     "llmseg_sumsq": [_p, _i64, C.c_int, _p, _p, _i64, _p],
     "llmseg_adamw": [_p, _p, _p, C.c_int, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _p, _p],
@@ -198,7 +204,7 @@ def load():
     # ABI guard at load time: this binding's structs must be the library's (the entry points check `struct_size` per call as well)
     if lib.llmseg_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI version {lib.llmseg_version()} != {ABI_VERSION} of this binding (rebuild: llmseg_amd/csrc/build.sh)")
-    for which, st in enumerate((GemmArgs, AttnArgs, AttnBwdArgs, Dropout, GemmW8Args)):
+    for which, st in enumerate((GemmArgs, AttnArgs, AttnBwdArgs, Dropout, GemmW8Args, LoraDownArgs)):
         if lib.llmseg_struct_size(which) != C.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) = {C.sizeof(st)} here, {lib.llmseg_struct_size(which)} in the library")
     _lib = lib

@@ -226,6 +226,19 @@ def _drops(drop):
     return (rng, 2 * layer, p) + tuple(seg), (rng, 2 * layer + 1, p) + tuple(seg)
 
 
+def _lora_wgrads(g, d, H, x, a2, t2, s, drq):
+    """The four weight gradients of a rank-8 LoRA'd q|k|v projection: d = dqkv [M, 3H], x = the projection's input, a2 = [drop_q(x) Aq^T | drop_v(x) Av^T | 0],
+    t2 = [s dq Bq | s dv Bv | 0], g = the fp32 arena slots of (Aq, Bq, Av, Bv) or None each, drq = the q branch's dropout (the v branch is stream + 1).
+    -> [dAq, dBq, dAv, dBv], None where the gradient was added to its arena slot."""
+    gaq, gbq, gav, gbv = g
+    if all(t is not None for t in g):                                    # arena mode: the four gradients in ONE launch (+ one fold), off the main chain
+        Leaves.run(lambda: ops.lora_wgrads(d, H, x, a2, t2, gbq, gbv, gaq, gav, s, drop=drq), d, x, t2, a2)
+        return [None] * 4
+    dbq, dbv = ops.lora_outer(d[:, :H], a2[:, :8], alpha=s, out=gbq, a2=d[:, 2 * H:], b2=a2[:, 8:16], out2=gbv)          # [H, 8] = s d^T (drop(x) A^T)
+    daq, dav = ops.lora_outer(x, t2[:, :8], out_rn=True, out=gaq, drop=drq, a2=x, b2=t2[:, 8:16], out2=gav)              # [8, H] = t^T drop(x)
+    return [None if gt is not None else t.to(BF16) for gt, t in ((gaq, daq), (gbq, dbq), (gav, dav), (gbv, dbv))]
+
+
 class LoraQKVFn(Function):
     """qkv = x Wqkv^T with the LoRA deltas of q_proj and v_proj added in place:
     q += s (drop(x) Aq^T) Bq^T, v += s (drop(x) Av^T) Bv^T, s = alpha / r, independent dropout masks on the two LoRA branch inputs
@@ -273,24 +286,14 @@ class LoraQKVFn(Function):
             drq = _drops(ctx.drop)[0]                                        # stream of the q branch; the v branch is stream + 1
             t2 = torch.empty((M, 64), device=d.device, dtype=BF16)       # [s dq Bq | s dv Bv | 0]
             ops.lora_down(dq, ctx.bt[:8], alpha=s, out=t2, zero_cols=48, x2=dv, w2=ctx.bt[8:])      # B^T packed in the forward: K-contiguous rows
-            tq, tv = t2[:, :8], t2[:, 8:16]
-            if ctx.wqkv_t is not None and ctx.drop is None:               # dx = d Wqkv + tq Aq + tv Av in ONE GEMM
+            if ctx.wqkv_t is not None and ctx.drop is None:              # dx = d Wqkv + tq Aq + tv Av in ONE GEMM
                 w2a = torch.empty((H, 64), device=d.device, dtype=BF16)
                 ops.lora_pack(aq, bq, av, bv, s, w2a=w2a)
                 dx = ops.gemm(d, ctx.wqkv_t, a2=t2, w2=w2a)
             else:                                                         # dropout masks the LoRA branches' dx element-wise
                 dx = ops.gemm(d, ctx.wqkv_t) if ctx.wqkv_t is not None else ops.gemm(d, wqkv, trans_w=True)
                 ops.lora_apply_(dx, t2, aq, w_rn=True, drop=drq, w2=av)
-            def wgrads():
-                b_ = ops.lora_outer(dq, xaq, alpha=s, out=gbq, a2=dv, b2=xav, out2=gbv)               # [H, 8] = s d^T (drop(x) A^T)
-                a_ = ops.lora_outer(x, tq, out_rn=True, out=gaq, drop=drq, a2=x, b2=tv, out2=gav)      # [8, H] = t^T drop(x)
-                return b_, a_
-            if all(g is not None for g in ctx.g):                            # arena mode: the four gradients in ONE launch (+ one fold), off the main chain
-                Leaves.run(lambda: ops.lora_wgrads(d, H, x, a2, t2, gbq, gbv, gaq, gav, s, drop=drq), d, x, t2, a2)
-                dbq = dbv = daq = dav = None
-            else:
-                (dbq, dbv), (daq, dav) = wgrads()
-            outs = [None if (g is not None or t is None) else t.to(BF16) for g, t in ((gaq, daq), (gbq, dbq), (gav, dav), (gbv, dbv))]
+            outs = _lora_wgrads(ctx.g, d, H, x, a2, t2, s, drq)
             return dx, None, outs[0], outs[1], outs[2], outs[3], None, None, None, None
         tq = ops.gemm(dq, bq, trans_w=True, alpha=s)                      # [M, r] = s dq Bq
         tv = ops.gemm(dv, bv, trans_w=True, alpha=s)
@@ -333,7 +336,6 @@ class NormLoraQKVFn(Function):
         s, H = ctx.s, wqkv.shape[1]
         d = d.contiguous()
         M = d.shape[0]
-        gaq, gbq, gav, gbv = ctx.g
         drq = _drops(ctx.drop)[0]
         t2 = torch.empty((M, 64), device=d.device, dtype=BF16)       # [s dq Bq | s dv Bv | 0]
         # the rank-8 down projection leaves its K-slice partials: the dX product's tail finishes them (and writes t2 for the weight gradients below)
@@ -344,13 +346,7 @@ class NormLoraQKVFn(Function):
             ops.lora_down(d[:, :H], ctx.bt[:8], alpha=s, out=t2, zero_cols=48, x2=d[:, 2 * H:], w2=ctx.bt[8:])
         dres = None if dpass is None else dpass.contiguous()
         dx = ops.gemm(d, ctx.wqkv_t, normbwd=(x, norm_w, ctx.eps, True, dres), nb_lora=(t2, aq, av, 1.0, drq, part, pS, pscale, 48))
-        if all(g is not None for g in ctx.g):                            # arena mode: the four gradients in ONE launch (+ one fold), off the main chain
-            Leaves.run(lambda: ops.lora_wgrads(d, H, h, a2, t2, gbq, gbv, gaq, gav, s, drop=drq), d, h, t2, a2)
-            outs = [None] * 4
-        else:
-            dbq, dbv = ops.lora_outer(d[:, :H], a2[:, :8], alpha=s, out=gbq, a2=d[:, 2 * H:], b2=a2[:, 8:16], out2=gbv)
-            daq, dav = ops.lora_outer(h, t2[:, :8], out_rn=True, out=gaq, drop=drq, a2=h, b2=t2[:, 8:16], out2=gav)
-            outs = [None if (g is not None or t is None) else t.to(BF16) for g, t in ((gaq, daq), (gbq, dbq), (gav, dav), (gbv, dbv))]
+        outs = _lora_wgrads(ctx.g, d, H, h, a2, t2, s, drq)
         return dx, None, None, None, None, outs[0], outs[1], outs[2], outs[3], None, None, None, None
 
 

@@ -18,7 +18,6 @@
 #include "llmseg_hip.h"
 #include <algorithm>
 #include <cstdlib>
-#define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
 
 namespace {
 

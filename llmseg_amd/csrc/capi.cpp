@@ -35,6 +35,7 @@ extern "C" int64_t llmseg_struct_size(int which) {
     case 2: return (int64_t)sizeof(llmseg_attn_bwd_args);
     case 3: return (int64_t)sizeof(llmseg_dropout);
     case 4: return (int64_t)sizeof(llmseg_gemm_w8_args);
+    case 5: return (int64_t)sizeof(llmseg_lora_down_args);
     default: return -1;
   }
 }

@@ -164,6 +164,32 @@ __device__ __forceinline__ void dropout8(float* f, unsigned long idx, uint32_t s
     f[j] = field >= thr ? f[j] * scale : 0.f;
   }
 }
+// llmseg_dropout as the kernels take it.  Internal linkage, like the file-local kernels whose signatures name it.
+namespace {
+constexpr int LR = 8;                                                                            // the LoRA rank of the rank-8 kernels
+struct DropP { const unsigned long* rng; uint32_t stream, thr; float scale; uint32_t seg; };     // thr == 0: no dropout; seg: rows per segment (0 = none)
+
+// Philox counter index of the 8 elements starting at (row m, column k) of a dense [M][width] activation, and what to add to the stream's
+// offset: with segments (llmseg_dropout.seg_rows) segment s = m / seg draws the mask of a separate pass at offset + s over its own rows.
+__device__ __forceinline__ unsigned long drop_index(const DropP& dp, unsigned long m, unsigned long width, unsigned long k, uint32_t& off_add) {
+  off_add = 0;
+  if (dp.seg) {
+    off_add = (uint32_t)(m / dp.seg);
+    m -= (unsigned long)off_add * dp.seg;
+  }
+  return (m * width + k) >> 3;
+}
+
+inline DropP make_drop(const llmseg_dropout* d) {
+  DropP dp{nullptr, 0u, 0u, 1.f, 0u};
+  if (d && d->rng_state && d->drop_thr > 0) {
+    dp.rng = (const unsigned long*)d->rng_state; dp.stream = d->stream; dp.thr = d->drop_thr; dp.seg = d->seg_rows;
+    dp.scale = 65536.f / (65536.f - (float)d->drop_thr);
+  }
+  return dp;
+}
+}  // namespace
+#define LL_DROP_OK(d) (!(d) || (d)->drop_thr < 65536u)
 
 
 // ---- fixed-order reductions (round 4) ------------------------------------------------------------------------------------------------
@@ -195,6 +221,8 @@ static __global__ __launch_bounds__(256) void fold_column_kernel(const float* __
   if (threadIdx.x == 0) out[i] += scale * s;
 }
 static inline unsigned fold_grid(long n) { const long g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g)); }
+// workgroups of 256 threads for a grid-stride kernel over `total` items
+static inline unsigned grid_for(long total) { const long g = (total + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
 
 // every kernel launch of the library goes through this macro: llmseg_launch_count() lets a benchmark report launches per micro-step
 void llmseg_count_launch();
@@ -218,6 +246,7 @@ extern "C" __attribute__((visibility("hidden"))) int llmseg_reduce_lora_normbwd(
 extern "C" __attribute__((visibility("hidden"))) int llmseg_lora_down_finish(const float* part, int S, void* y, int64_t ldy, int64_t M, float scale, int zero_cols, int nb, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int llmseg_attn_delta128(const void* O, int64_t ldo, const void* dO, int64_t lddo, float* delta, int64_t batch, int32_t heads,
                                                                           int64_t T, void* stream);
+#define AL16(p) ((((uintptr_t)(p)) & 15) == 0)          // 16-byte aligned (true for NULL: an absent operand)
 #define LL_CHECK(cond, ...)                 \
   do {                                      \
     if (!(cond)) {                          \

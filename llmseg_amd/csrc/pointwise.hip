@@ -336,14 +336,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_t* __restri
   }
 }
 
-inline unsigned grid_for(long total) {
-  long g = (total + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 }  // namespace
-
-#define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
 
 extern "C" int llmseg_norm(const void* x, const void* w, const void* b, void* y, int64_t rows, int64_t cols, int64_t ldx, int64_t ldy,
                            float eps, int rms, const int32_t* row_map, void* stream) {

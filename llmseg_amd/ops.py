@@ -860,8 +860,8 @@ def lora_down(x, w, w_kr=False, alpha=1.0, out=None, zero_cols=0, drop=None, x2=
     """y [M, 8] = alpha * drop(x) [M, K] @ W^T; W stored [8, K] (or [K, 8] when w_kr).  x may be a column view (row stride = ld).
     With (x2, w2) the second branch lands in columns 8..15 of the same rows (its dropout stream is drop's + 1; x2 may be x).  `out`
     may be the leading columns of a wider row; `zero_cols` further columns of every row are zero-filled.
-    pack = (aq, bq, av, bv, s, w2b, w2a, bt): `lora_pack` of the same layer in the same call (`llmseg_lora_down_pack`: it rides in the K-slice finish launch).
-    parts=True (`llmseg_lora_down_parts`): -> (y, partials | None, S, scale): where the product runs as K slices it is left UNFINISHED (y not written; hand
+    pack = (aq, bq, av, bv, s, w2b, w2a, bt): `lora_pack` of the same layer in the same call (`llmseg_lora_down_args.pack_*`: it rides in the K-slice finish launch).
+    parts=True (`llmseg_lora_down_args.parts_S`): -> (y, partials | None, S, scale): where the product runs as K slices it is left UNFINISHED (y not written; hand
     (partials, S, scale, zero_cols) to `gemm(..., nb_lora=)`, whose tail finishes it and writes y); S = 0: y is complete.
     scratch=False: no K-slice scratch is handed over (the product runs unsliced)."""
     M, K = x.shape
@@ -871,23 +871,22 @@ def lora_down(x, w, w_kr=False, alpha=1.0, out=None, zero_cols=0, drop=None, x2=
     want_scratch, scratch = scratch, None
     if want_scratch and not w_kr and (M + 15) // 16 < 256 and K % 256 == 0:       # short activations: K-sliced over several workgroups per row tile (fp32 partials)
         scratch = torch.empty((32 * 2 * M * 16,), device=x.device, dtype=torch.float32)
-    args = (_ptr(x), _ptr(x2 if w2 is not None and x2 is not None else (x if w2 is not None else None)), x.stride(0),
-            _ptr(w), _ptr(w2), _ptr(y), y.stride(0), M, K, 1 if w_kr else 0, alpha, zero_cols, _drop(drop),
-            _ptr(scratch), 0 if scratch is None else scratch.numel() * 4)
+    assert not (parts and pack is not None)
+    dr = _drop(drop)
+    a = _lib.LoraDownArgs(x0=_ptr(x), x1=_ptr(x2 if w2 is not None and x2 is not None else (x if w2 is not None else None)), ldx=x.stride(0),
+                          w0=_ptr(w), w1=_ptr(w2), y=_ptr(y), ldy=y.stride(0), M=M, K=K, w_kr=1 if w_kr else 0, alpha=alpha, zero_cols=zero_cols,
+                          drop=None if dr is None else C.cast(dr, _lib._dp), scratch=_ptr(scratch), scratch_bytes=0 if scratch is None else scratch.numel() * 4)
+    S_out, sc_out = C.c_int32(0), C.c_float(0.0)
     if parts:
-        assert pack is None
-        S_out, sc_out = C.c_int32(0), C.c_float(0.0)
-        _lib.check(_lib.load().llmseg_lora_down_parts(*args, C.byref(S_out), C.byref(sc_out), _stream()), "lora_down_parts")
-        return y, (scratch if S_out.value > 0 else None), S_out.value, sc_out.value
-    if pack is None:
-        _lib.check(_lib.load().llmseg_lora_down_ws(*args, _stream()), "lora_down")
-    else:
-        aq, bq, av, bv, ps, w2b, w2a, bt = pack
+        a.parts_S, a.parts_scale = C.pointer(S_out), C.pointer(sc_out)
+    if pack is not None:
+        aq, bq, av, bv, a.pack_s, w2b, w2a, bt = pack
         for t in (aq, bq, av, bv):
             assert t.is_contiguous()
-        _lib.check(_lib.load().llmseg_lora_down_pack(*args, _ptr(aq), _ptr(bq), _ptr(av), _ptr(bv), _ptr(w2b), _ptr(w2a), _ptr(bt), aq.shape[1], ps, _stream()),
-                   "lora_down_pack")
-    return y
+        a.pack_aq, a.pack_bq, a.pack_av, a.pack_bv, a.pack_w2b, a.pack_w2a, a.pack_bt = (_ptr(t) for t in (aq, bq, av, bv, w2b, w2a, bt))
+        a.pack_H = aq.shape[1]
+    _lib.check(_lib.load().llmseg_lora_down(C.byref(a), _stream()), "lora_down")
+    return (y, (scratch if S_out.value > 0 else None), S_out.value, sc_out.value) if parts else y
 
 
 def lora_outer(a, b, out_rn=False, alpha=1.0, out=None, drop=None, a2=None, b2=None, out2=None, workspace=_DEFAULT_WS):

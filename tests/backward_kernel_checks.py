@@ -1,4 +1,4 @@
-"""Backward, LoRA and optimizer kernels (llmseg_amd/csrc/backward.hip, the CE forward of head.hip) on every dispatch route: a case table,
+"""Backward, LoRA and optimizer kernels (llmseg_amd/csrc/backward.hip and lora.hip, the CE forward of head.hip) on every dispatch route: a case table,
 input builders, fp64 references, LOCAL tolerances, fp32 / bf16 emulations of what the kernels round, and mutants (fp64 results of subtly
 wrong problems) that the tolerances must reject.
 
@@ -242,7 +242,11 @@ def cases():
                         ("2100x264_rw4", 1, dict(M=2100, K=264, same=0)), ("2100x264_rw4_nb1_zc48_drop_seg", 1, dict(M=2100, K=264, nb=1, zc=48, wide=1, drop=1, seg=700)),
                         ("50x256_wkr", 1, dict(M=50, K=256, w_kr=1, zc=48, wide=1)), ("2100x264_wkr", 1, dict(M=2100, K=264, w_kr=1, drop=1)),
                         ("1x4096_S32", 2, dict(M=1, K=4096)), ("15x4096_S32", 2, dict(M=15, K=4096, same=0, drop=1)), ("16x4096_S32", 2, dict(M=16, K=4096, zc=48, wide=1)),
-                        ("17x4096_S32", 2, dict(M=17, K=4096, nb=1)), ("17x384_S1", 1, dict(M=17, K=384, same=0))):
+                        ("17x4096_S32", 2, dict(M=17, K=4096, nb=1)), ("17x384_S1", 1, dict(M=17, K=384, same=0)),
+                        # parts=1 where the shape takes no K slices (per-row kernel; MFMA with S = 1; MFMA unsliced for want of scratch): S = 0 comes back, no
+                        # partials, y complete after the one launch and the same bits as the plain call
+                        ("37x136_rw1_parts_noslices", 1, dict(M=37, K=136, same=0, zc=48, wide=1, parts=1)), ("17x384_S1_parts_noslices", 1, dict(M=17, K=384, same=0, parts=1)),
+                        ("50x256_noscratch_parts_noslices", 1, dict(M=50, K=256, scratch=0, parts=1))):
         add("lora_down", name, l, **{**D, **kw})
     # ---- lora_outer / lora_wgrads
     for M, N, l in ((638, 4096, 1), (7656, 4096, 2), (50, 256, 2), (37, 264, 2), (1, 8, 2), (5, 72, 2)):      # l: launches of lora_wgrads (nz = 4); lora_outer always slices here
@@ -724,7 +728,7 @@ def lora_down_inputs(case):
     x2 = x if case.same else torch.randn(M, K, generator=g).to(BF)
     w = [(torch.randn(8, K, generator=g) * K ** -0.5 + 0.3 * K ** -0.5).to(BF) for _ in range(2)]
     inp = dict(x=x, x2=x2, w0=w[0], w1=w[1])
-    if case.p.get("parts"):              # the dX product whose norm-backward tail finishes the K-slice partials: d [M, 3K] . wt [K, 3K]^T, pre-norm input nx, weight nw, LoRA A matrices
+    if case.p.get("parts") and route(case)[0] > 1:      # the dX product whose norm-backward tail finishes the K-slice partials: d [M, 3K] . wt [K, 3K]^T, pre-norm input nx, weight nw, LoRA A matrices
         Kg = 3 * K
         inp.update(d=(torch.randn(M, Kg, generator=g) * 0.3).to(BF), wt=(torch.randn(K, Kg, generator=g) * Kg ** -0.5).to(BF), nx=torch.randn(M, K, generator=g).to(BF),
                    nw=torch.randn(K, generator=g).to(BF), a0=(torch.randn(8, K, generator=g) * 0.1).to(BF), a1=(torch.randn(8, K, generator=g) * 0.1).to(BF))

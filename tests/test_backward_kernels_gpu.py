@@ -1,4 +1,4 @@
-"""GPU: the backward, LoRA and optimizer kernels (llmseg_amd/csrc/backward.hip, the CE forward of head.hip) on every dispatch route against fp64
+"""GPU: the backward, LoRA and optimizer kernels (llmseg_amd/csrc/backward.hip and lora.hip, the CE forward of head.hip) on every dispatch route against fp64
 references, under the local tolerances that tests/test_backward_kernels_cpu.py validates against emulations and mutants.  Every case also asserts
 the number of library launches its call makes (the proof that it still reaches the route it was written for), that the guard region around every
 output it hands over is untouched, and -- for the reductions -- that the same call twice gives the same bits."""
@@ -155,6 +155,15 @@ def run_lora_down(case, inp, ops):
     outs["y"] = lambda: o["y"].full[:, :8 * nb + zc]                 # the allocated rows beyond M with it: the reference holds NaN there
     if not case.parts:
         return (lambda: ops.lora_down(x, wk, **kw)), outs, list(o.values())
+    if bk.route(case)[0] <= 1:                                       # no K slices on this shape: S = 0, no partials, y complete after the one launch
+        plain = Out(M, 8 * nb + zc, BF, NAN, ld=o["y"].full.shape[1], alloc_rows=M + bk.PAD_ROWS)
+        ops.lora_down(x, wk, **{**kw, "out": plain.full[:M] if case.wide else plain.w})      # the plain call of the same case (outside the counted launches)
+
+        def call_noslices():
+            _, part, S, sc = ops.lora_down(x, wk, parts=True, **kw)
+            assert part is None and S == 0 and sc == bk.ALPHA, (part, S, sc)      # the finish factor is reported all the same (no dropout here: alpha)
+            assert torch.equal(_bits(o["y"].full), _bits(plain.full)), f"{case.name}: y differs from the plain call's"
+        return call_noslices, outs, list(o.values())
     d, wt, nx, nw, a0, a1 = (_d(inp[k]) for k in ("d", "wt", "nx", "nw", "a0", "a1"))
 
     def call():              # the K-slice partials are left unfinished; the norm-backward tail of the dX product finishes them and writes y

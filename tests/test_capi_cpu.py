@@ -49,7 +49,8 @@ def test_struct_layouts_header_binding_library_and_integration_stub():
     from llmseg_amd import _lib
     lib = _lib.load()
     for which, (cname, st) in enumerate((("llmseg_gemm_args", _lib.GemmArgs), ("llmseg_attn_args", _lib.AttnArgs),
-                                         ("llmseg_attn_bwd_args", _lib.AttnBwdArgs), ("llmseg_dropout", _lib.Dropout))):
+                                         ("llmseg_attn_bwd_args", _lib.AttnBwdArgs), ("llmseg_dropout", _lib.Dropout),
+                                         ("llmseg_gemm_w8_args", _lib.GemmW8Args), ("llmseg_lora_down_args", _lib.LoraDownArgs))):
         assert [f[0] for f in st._fields_] == _header_struct_fields(cname), cname
         assert lib.llmseg_struct_size(which) == C.sizeof(st), cname
     assert lib.llmseg_struct_size(99) == -1
@@ -80,6 +81,25 @@ def test_abi_guard_rejects_a_stale_struct():
     b = _lib.AttnBwdArgs()
     b.struct_size += 8
     assert lib.llmseg_attn_bwd(C.byref(b), None) == -1 and b"ABI mismatch" in lib.llmseg_last_error()
+    d = _lib.LoraDownArgs(M=1, K=8)
+    assert d.struct_size == C.sizeof(_lib.LoraDownArgs)
+    d.struct_size -= 8
+    assert lib.llmseg_lora_down(C.byref(d), None) == -1 and b"ABI mismatch" in lib.llmseg_last_error()
+
+
+def test_lora_down_refuses_partials_and_a_pack_job_together():
+    """Leaving the K-slice partials and carrying a pack job exclude each other: LLMSEG_EINVAL before any other argument is looked at and before any launch
+    (no device needed); so does one of the two parts pointers without the other."""
+    import ctypes as C
+    from llmseg_amd import _lib
+    lib = _lib.load()
+    S, sc, buf = C.c_int32(-7), C.c_float(-7.0), (C.c_char * 64)()
+    n0 = lib.llmseg_launch_count()
+    a = _lib.LoraDownArgs(M=1, K=8, parts_S=C.pointer(S), parts_scale=C.pointer(sc), pack_aq=C.addressof(buf))
+    assert lib.llmseg_lora_down(C.byref(a), None) == -1 and b"not both" in lib.llmseg_last_error()
+    a = _lib.LoraDownArgs(M=1, K=8, parts_S=C.pointer(S))
+    assert lib.llmseg_lora_down(C.byref(a), None) == -1 and b"both set or both NULL" in lib.llmseg_last_error()
+    assert lib.llmseg_launch_count() == n0 and S.value == -7 and sc.value == -7.0
 
 
 def test_product_does_not_import_oracle():

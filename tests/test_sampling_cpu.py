@@ -33,7 +33,7 @@ def test_symbol_is_declared_bound_and_exported_with_the_headers_argument_order()
     assert int(re.search(r"#define LLMSEG_ABI_VERSION (\d+)", src).group(1)) == _lib.ABI_VERSION >= 16
     lib = _lib.load()
     assert hasattr(lib, "llmseg_sample_tokens")
-    assert lib.llmseg_struct_size(5) == -1                                   # a plain argument list: no new argument struct
+    assert lib.llmseg_struct_size(6) == -1                                   # a plain argument list: no argument struct of its own (5, the last index, is llmseg_lora_down_args)
     assert re.search(r"llmseg_version\(\) == %d\b" % _lib.ABI_VERSION, open(os.path.join(ROOT, "INTEGRATION.md")).read())
     assert "sample.hip" in open(os.path.join(ROOT, "llmseg_amd", "csrc", "build.sh")).read()
 

@@ -44,7 +44,7 @@ def test_symbols_and_struct_agree_in_header_binding_and_library():
     for name in ("llmseg_quantize_rows_i8", "llmseg_gemm_w8"):
         assert hasattr(lib, name), name
     assert lib.llmseg_struct_size(4) == C.sizeof(_lib.GemmW8Args)
-    assert lib.llmseg_struct_size(5) == -1
+    assert lib.llmseg_struct_size(6) == -1                                   # (5 is llmseg_lora_down_args)
     assert re.search(r"llmseg_version\(\) == %d\b" % _lib.ABI_VERSION, open(os.path.join(ROOT, "INTEGRATION.md")).read())
 
 
