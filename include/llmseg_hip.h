@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args, 5 = llmseg_lora_down_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 17
+#define LLMSEG_ABI_VERSION 18
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -193,6 +193,33 @@ int llmseg_sample_tokens(const void* logits, int64_t ldl, int64_t N, int64_t V, 
                          int64_t eos, int64_t pad, int64_t* unfinished /* nullable, in/out */, int64_t* next, float* logprob /* nullable */,
                          int32_t* kept /* nullable */, float* probs /* nullable */, int64_t ldp, void* stream);
 
+/* ---- beam search (generate(num_beams >= 2)): one pick per token, TWO launches ----
+ * N prompts, B = num_beams live beams each (2 <= B <= 16), V >= 2 B.  Inputs: logits bf16 [N * beams_in][ldl] (beams_in = 1 for the first pick, which reads the
+ * prefill's one row per prompt; B afterwards), beam_scores fp32 [N * beams_in], done int32 [N], src_in int32 [N * B][ld_src], pos_rows int32 [N * B] (the position
+ * of the token about to be fed to each row).  Per prompt n that is not done, in exact arithmetic:
+ *   1. candidate (b, v) has score s_b + log_softmax(l_b)_v; rank the beams_in * V candidates by score descending, equal scores by the SMALLER flat index b * V + v,
+ *      and take the best 2 B.
+ *   2. walk them in rank order: an eos candidate (v == eos, eos >= 0) of rank < B is recorded, fin_parent[n][k] = b, fin_score[n][k] = its score, k counting from 0 in
+ *      rank order, fin_count[n] = their number; an eos candidate of rank >= B is dropped; any other candidate fills the next free slot i < B:
+ *      next_token[n B + i] = v, parent[n B + i] = b (the slot within the prompt, 0 .. beams_in - 1), next_scores[n B + i] = its score.  At most one candidate per
+ *      beam is eos, so B slots are always filled.  step_best[n] = the score of rank 0.
+ * A done prompt (done[n] != 0): next_token = pad, parent = own slot, next_scores = beam_scores unchanged, fin_count[n] = 0, step_best[n] = 0.
+ * The table, for row r = n B + i with parent j and p = pos_rows[r]: src_out[r][t] = src_in[n B + j][t] for t < p - 1, src_out[r][p - 1] = n B + j (where the parent
+ * wrote the key of the token it was just fed).  First pick (beams_in == 1; no decode step has run, the prefill's K and V lie in physical row n B only):
+ * src_out[r][t] = n B for every t < p, src_in is not read.  Entries t >= p of src_out are NOT WRITTEN (they keep what the buffer held).  src_in == src_out is refused
+ * (LLMSEG_EINVAL): one row's copy would read another row's output.
+ * Arithmetic: with l_max the row's largest logit, a weight is e = expf(l - l_max) in fp32, held as the integer floor(e * 2^40); S = their INTEGER sum (associative:
+ * any order gives the same bits); lse = fp32(ln(S) - 40 ln 2), the logarithm in fp64; score = fl(s_b + fl(fl(l - l_max) - lse)), three fp32 operations rounded once
+ * each.  No floating-point atomics and no floating-point sum: the result is a pure function of the inputs, and two candidates of one row with equal bf16 logits get
+ * EQUAL scores, so the flat-index rule is exact within a row.  The ranking compares these fp32 scores.
+ * Checked before any launch: pointers (all required) and their alignment, 2 <= B <= 16, beams_in in {1, B}, 2 B <= V <= 2^22, ldl >= V, ld_src >= 1, eos < V,
+ * pad >= 0, N >= 1, workspace_bytes >= N * beams_in * 2 B * 8 (8-byte aligned device memory, overwritten).  pos_rows[r] is clamped to ld_src.  A row with fewer than
+ * 2 B finite logits, or with a NaN, gives unspecified tokens in [0, V) and parents in [0, beams_in). */
+int llmseg_beam_step(const void* logits, int64_t ldl, const float* beam_scores, const int32_t* done, int64_t eos, int64_t pad, const int32_t* src_in,
+                     int32_t* src_out, int64_t ld_src, const int32_t* pos_rows, int64_t N, int32_t B, int32_t beams_in, int64_t V, int64_t* next_token,
+                     int32_t* parent, float* next_scores, float* step_best, int32_t* fin_count, int32_t* fin_parent, float* fin_score, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 /* ---- fused attention forward -----------------------------------------------------------------
  * O[b][h][q][:] = softmax_k( scale * Q.K^T + bias + mask ) V, online softmax in fp32, bf16 MFMA.
  * Q/K/V/O are addressed as base + b*stride_b + h*stride_h + row*stride_row (elements); head_dim in {32,64,80,128}.
@@ -314,6 +341,16 @@ int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos, const floa
 int llmseg_decode_attn_rows(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                             const int32_t* pos_rows_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
                             void* scratch, int64_t scratch_bytes, void* stream);
+/* llmseg_decode_attn_rows over a BEAM-INDEXED cache (beam search: the cache is never re-ordered, a table is).  R = N rows (prompts x beams); src int32
+ * [R][ld_src] in device memory.  Write side as llmseg_decode_attn_rows: row r at pos = pos_rows_dev[r] rotates q and k and writes k / v to the physical slot
+ * [r][pos].  Read side: it attends to keys t = 0 .. pos; key t < pos is read from physical row src[r][t], i.e. from kcache + src[r][t] * cache_stride_n + t * D
+ * (D = heads * head_dim; vcache alike), key pos is the row's own new key (src[r][pos] is NOT read, nor any entry beyond it).  Entries of src are TRUSTED to
+ * lie in [0, R): they are not checked, an entry outside reads outside the cache.  Checked before the launch: everything llmseg_decode_attn_rows checks, src
+ * non-NULL and 4-byte aligned, ld_src >= capacity > 0 (capacity = the caches' positions per row: every position is < capacity).  Split count, scratch layout, key
+ * groups and merge are llmseg_decode_attn_rows's with N := R: a table with src[r][t] == r gives its bits, in the output and in both caches. */
+int llmseg_decode_attn_beams(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                             const int32_t* pos_rows_dev, const int32_t* src, int64_t ld_src, int64_t capacity, int64_t N, int32_t heads, int32_t head_dim,
+                             float scale, void* out, int64_t ldo, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* y[i] = act(x[i]), bf16, n % 8 == 0, in place allowed (the GELU between LayerNorm2d and the second transposed convolution of SAM's
  * mask decoder, mask_decoder.py:53-63: every other activation on the path rides in a GEMM epilogue) */

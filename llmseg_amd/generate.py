@@ -59,6 +59,7 @@ class DecodeState:
         self.bits = None             # weight_bits of the captured step (None = bf16 weights)
         self.ragged = False          # the captured step reads pos_rows (one position per sequence) instead of pos
         self.w8 = None               # weight_bits = 8: {layer-matrix name: (q int8, scale fp32, w_hat bf16)} of `_quantize_w8`
+        self.beam_src = None         # beam search over the never-moved cache: int32 [N, capacity], key t of row r lives in physical row beam_src[r, t]
 
 
 class GenerateMixin:
@@ -116,7 +117,7 @@ class GenerateMixin:
                     qkv = ops.gemm(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), wq)
                 if hd == 128:                                  # RoPE + KV append + attention over the cache: one launch (+ the split's merge)
                     if st.ragged:                              # every sequence at its own position: RoPE angle, cache slot and key count
-                        ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True)
+                        ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True, beam_src=st.beam_src)
                     else:
                         ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
                 else:
@@ -245,10 +246,10 @@ class GenerateMixin:
         for i in range(c.layers):
             p = f"model.layers.{i}."
             q8 = lambda name: st.w8[p + name][:2]
-            qkv = ops.gemm_w8(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), *q8("qkv"))
+            qkv = self._gemm_w8_rows(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), *q8("qkv"))
             if hd == 128:                                  # RoPE + KV append + attention over the cache: one launch (+ the split's merge)
                 if st.ragged:
-                    ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True)
+                    ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True, beam_src=st.beam_src)
                 else:
                     ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
             else:
@@ -256,12 +257,24 @@ class GenerateMixin:
                 ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)
                 ops.attention(qkv, st.k[i], st.v[i], att, batch=N, heads=heads, Nq=1, Nk=st.cap, head_dim=hd, q_strides=(ld, hd, ld),
                               k_strides=(st.cap * H, hd, H), v_strides=(st.cap * H, hd, H), o_strides=(H, hd, H), nk_dev=st.pos[1:])
-            x = ops.gemm_w8(att, *q8("self_attn.o_proj.weight"), residual=x)
-            gu = ops.gemm_w8(F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True), *q8("gate_up"))
-            x = ops.gemm_w8(ops.swiglu(gu, c.inter), *q8("mlp.down_proj.weight"), residual=x)
+            x = self._gemm_w8_rows(att, *q8("self_attn.o_proj.weight"), residual=x)
+            gu = self._gemm_w8_rows(F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True), *q8("gate_up"))
+            x = self._gemm_w8_rows(ops.swiglu(gu, c.inter), *q8("mlp.down_proj.weight"), residual=x)
         ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
         ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)          # lm_head stays bf16: 2 % of the stream, and it decides the arg-max
         (st.pos_rows if st.ragged else st.pos).add_(1)
+
+    @staticmethod
+    def _gemm_w8_rows(a, q, scale, residual=None):
+        """`ops.gemm_w8` (at most 8 rows a call) on any number of rows: up to 8 rows it IS that call; more rows (prompts x beams) go in chunks of 8, each
+        streaming the weights again."""
+        M = a.shape[0]
+        if M <= 8:
+            return ops.gemm_w8(a, q, scale, residual=residual)
+        out = torch.empty((M, q.shape[0]), device=a.device, dtype=BF16)
+        for r in range(0, M, 8):
+            ops.gemm_w8(a[r:r + 8], q, scale, residual=None if residual is None else residual[r:r + 8], out=out[r:r + 8])
+        return out
 
     def _decode_step(self, st, use_graph=True):
         """Run one decode step; from the second step of a state on, replay it from a hipGraph (captured once per (N, capacity): a step is
@@ -282,8 +295,8 @@ class GenerateMixin:
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
                  weight_bits=None, attention_mask=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None,
-                 return_logprobs=False):
-        """Greedy generation (or sampling: do_sample, below).  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
+                 return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False, return_beam_scores=False, beam_cache="indirect", _beam_trace=None):
+        """Greedy generation (or sampling: do_sample, or beam search: num_beams, both below).  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
         IMAGE_TOKEN_INDEX each.
         -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
         attention_mask (bool [N, L], None = every token is a prompt token): prompts of different lengths, RIGHT-padded (`pad_prompts` builds
@@ -308,7 +321,40 @@ class GenerateMixin:
         the loop from `torch.Generator(device).manual_seed(seed)` (seed=None: torch's global generator), or given as `uniforms=` (not both); step
         s of row n consumes uniforms[n, s], so a call is a pure function of (weights, prompt, arguments, uniforms).  With do_sample=False the
         sampling arguments must stay at their defaults.  return_logprobs=True (sampling only) adds a third result: fp32 [N, n_new], ln of the
-        renormalised probability each token was drawn with (0 where a finished row emitted pad_token_id)."""
+        renormalised probability each token was drawn with (0 where a finished row emitted pad_token_id).
+        num_beams >= 2: beam search by the rule of Hugging Face's scorer as include/llmseg_hip.h (`llmseg_beam_step`) and tests/beam_checks.py restate it --
+        per token the 2 * num_beams best continuations of a prompt's live beams, eos candidates of rank < num_beams become finished hypotheses of value
+        sum / length ** length_penalty (the eos counts), a prompt is done once it holds num_beams hypotheses and (early_stopping=True, or) its worst is at
+        least the step's best candidate / length ** length_penalty; the result per prompt is its best hypothesis, the live beams included when
+        max_new_tokens ends the loop.  The prompt is prefilled ONCE per prompt; the decode state has N * num_beams rows; the pick is one `ops.beam_step`
+        (two launches) and one small device-to-host copy per token.  beam_cache="indirect" (default): the KV cache is never moved, every beam reads key t
+        from the physical row a [rows, capacity] int32 table names (`llmseg_decode_attn_beams`) and the pick re-orders the table; beam_cache="copy": the same
+        loop re-orders K and V physically (`index_select` over every layer) and runs the `llmseg_decode_attn_rows` step -- the same bits, kept as the
+        yardstick (profiles/beam_search.md).  Results: sequences [N, L + n_new] with n_new the longest winning length, row i = its prompt, its tokens (eos
+        included), then pad_token_id; hidden [N, T + n_new - 1, H] = row i's T prefill states, the state of each fed token of the winner, then zeros;
+        return_beam_scores=True adds fp32 [N], the winner's value.  weight_bits=8 and use_graph work as in the greedy route.  Out of scope (ValueError):
+        do_sample together with beams (beam sampling); an attention_mask that is ragged after trimming; fuse_decode=False; head_dim != 128; num_beams > 16 or
+        2 * num_beams > vocab; early_stopping="never"; several returned sequences, diverse groups and constraints have no argument.  With num_beams == 1
+        the other beam arguments must stay at their defaults, and not one launch of the routes above changes."""
+        if not (isinstance(num_beams, int) and not isinstance(num_beams, bool) and num_beams >= 1):
+            raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
+        if beam_cache not in ("indirect", "copy"):
+            raise ValueError(f"beam_cache must be 'indirect' or 'copy', got {beam_cache!r}")
+        if not isinstance(early_stopping, bool):
+            raise ValueError(f"early_stopping must be True or False ('never' is out of scope), got {early_stopping!r}")
+        if isinstance(length_penalty, bool) or not (isinstance(length_penalty, (int, float)) and math.isfinite(length_penalty)):
+            raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
+        if num_beams == 1 and not (length_penalty == 1.0 and early_stopping is False and not return_beam_scores and beam_cache == "indirect" and _beam_trace is None):
+            raise ValueError("length_penalty, early_stopping, return_beam_scores and beam_cache need num_beams >= 2")
+        if num_beams >= 2:
+            if do_sample:
+                raise ValueError("do_sample with num_beams >= 2 (beam sampling) is out of scope")
+            if not fuse_decode:
+                raise ValueError("num_beams >= 2 needs fuse_decode=True (the beam-indexed cache is built into the fused decode step only)")
+            if self.config.llama.head_dim != 128:
+                raise ValueError(f"num_beams >= 2 needs head_dim 128, got {self.config.llama.head_dim}: the two-launch route is out of scope")
+            if num_beams > 16 or 2 * num_beams > self.config.llama.vocab:
+                raise ValueError(f"num_beams must be <= 16 and 2 * num_beams <= vocab = {self.config.llama.vocab}, got {num_beams}")
         defaults = temperature == 1.0 and top_k == 0 and top_p == 1.0 and seed is None and uniforms is None and not return_logprobs
         if not do_sample and not defaults:
             raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True (greedy decoding takes none of them)")
@@ -329,6 +375,13 @@ class GenerateMixin:
             raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
         if weight_bits == 8 and not fuse_decode:
             raise ValueError("weight_bits=8 needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
+        if num_beams >= 2:
+            if not defaults:
+                raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True")
+            if weight_bits not in (None, 8):
+                raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
+            return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, weight_bits, attention_mask, num_beams,
+                                        float(length_penalty), early_stopping, return_beam_scores, beam_cache, _beam_trace)
         self.prepare()
         c = self.config
         cl = c.llama
@@ -432,6 +485,149 @@ class GenerateMixin:
         else:
             res = (torch.cat(seqs, 1), hidden[:, :T + n_new - 1])
         return res + (torch.cat(lps, 1),) if return_logprobs else res
+
+    def _generate_beams(self, images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, weight_bits, attention_mask, B, length_penalty,
+                        early_stopping, return_beam_scores, beam_cache, trace):
+        """`generate(num_beams=B >= 2)`: the arguments are checked there."""
+        if attention_mask is not None:
+            input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
+            if lens is not None:
+                raise ValueError("num_beams >= 2 with prompts of different lengths (an attention_mask that is ragged after trimming) is out of scope")
+        self.prepare()
+        c = self.config
+        cl = c.llama
+        dev = self.device_
+        N, L = input_ids.shape
+        R = N * B
+        Pn, H = c.n_img_tokens, cl.hidden
+        T = L - 1 + Pn
+        assert max_new_tokens >= 1
+        fill = 0 if pad_token_id is None else int(pad_token_id)
+        plan = self.make_plan(input_ids, None, torch.ones((N, L), dtype=torch.bool), list(range(N + 1)), None, inference=False)
+        F = _Direct
+        proj = self.encode_images(images_clip.to(dev, BF16))
+        embeds = F.embed_splice(input_ids.to(dev).contiguous(), self._w("model.embed_tokens.weight", F), proj[1:], Pn, (Pn + 1) * H, plan.tok_index)
+        cap = (T + max_new_tokens + 63) // 64 * 64
+        indirect = beam_cache == "indirect"
+        states = self.__dict__.setdefault("_decode_states", {})
+        st = states.get((R, cap, "beams", beam_cache))         # a state of its own: a greedy call on R sequences never meets a beam call's graph
+        if st is None:
+            st = states[(R, cap, "beams", beam_cache)] = DecodeState(cl.layers, R, cap, H, cl.vocab, dev)
+            st.fused, st.ragged = True, True                   # every row at its own device-side position (they are equal; the per-row kernels read them)
+            st.src_a = torch.zeros((R, cap), device=dev, dtype=torch.int32)      # the table, at a fixed address: the captured step reads it
+            st.src_b = torch.zeros((R, cap), device=dev, dtype=torch.int32)      # ... and the buffer `ops.beam_step` writes the re-ordered table to (copied back)
+            if indirect:
+                st.beam_src = st.src_a
+
+        def keep_kv(i, qkv):                                   # the prompt's K and V once per prompt: physical row n * B
+            st.k[i, ::B, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
+            st.v[i, ::B, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
+        if weight_bits is None:
+            st.w8 = None
+            hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
+        else:
+            st.w8 = self._quantize_w8()
+            hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
+        if weight_bits != st.bits:
+            st.bits, st.graph, st.warm = weight_bits, None, False
+        st.qkv_w = self._merge_lora() if (cl.lora_r > 0 and weight_bits is None) else None
+        emb_w = self._w("model.embed_tokens.weight", F)
+        st.pos_rows.fill_(T)
+        logits = ops.gemm(hidden_p[:, -1].contiguous(), self._w("lm_head.weight", F))      # [N, V]: the first pick reads one row per prompt
+        scores = torch.zeros((N,), device=dev, dtype=torch.float32)
+        done_dev = torch.zeros((N,), device=dev, dtype=torch.int32)
+        # the pick's small outputs in ONE buffer, so that one copy brings them to the host: step_best [N] | fin_count [N] | fin_parent [N, B] | fin_score [N, B]
+        rec = torch.zeros((2 * N + 2 * N * B,), device=dev, dtype=torch.int32)
+        ws = torch.empty((R * 2 * B,), device=dev, dtype=torch.int64)
+        row0 = torch.arange(R, device=dev) // B * B
+        done = [False] * N
+        pools = [[] for _ in range(N)]                         # per prompt: (value, kind, step, slot), the B best by value
+        toks, pars, hids = [], [], []
+        step = 0
+        while True:
+            out = dict(next_token=torch.empty((R,), device=dev, dtype=torch.int64), parent=torch.empty((R,), device=dev, dtype=torch.int32),
+                       next_scores=torch.empty((R,), device=dev, dtype=torch.float32), step_best=rec[:N].view(torch.float32), fin_count=rec[N:2 * N],
+                       fin_parent=rec[2 * N:2 * N + N * B].view(N, B), fin_score=rec[2 * N + N * B:].view(torch.float32).view(N, B))
+            ops.beam_step(logits, scores, done_dev, st.src_a, st.src_b, st.pos_rows, B, eos_token_id=eos_token_id, pad_token_id=fill, out=out, workspace=ws)
+            st.src_a.copy_(st.src_b)                           # (entries at or beyond a row's position are never read: whatever they hold is copied along)
+            rec_h = rec.cpu()                                  # the one host synchronisation of a step
+            if trace is not None:
+                trace.append(dict(logits=logits.float().cpu(), scores=scores.cpu(), done=list(done), next_token=out["next_token"].cpu(), parent=out["parent"].cpu(),
+                                  next_scores=out["next_scores"].cpu(), rec=rec_h.clone()))
+            toks.append(out["next_token"])
+            pars.append(out["parent"])
+            sb, fc = rec_h[:N].view(torch.float32).tolist(), rec_h[N:2 * N].tolist()
+            fp, fs = rec_h[2 * N:2 * N + N * B].view(N, B).tolist(), rec_h[2 * N + N * B:].view(torch.float32).view(N, B).tolist()
+            g = step + 1
+            for n in range(N):
+                if done[n]:
+                    continue
+                for k in range(fc[n]):
+                    self._beam_pool_add(pools[n], B, (fs[n][k] / g ** length_penalty, "eos", step, fp[n][k]))
+                if len(pools[n]) >= B and (early_stopping or min(h[0] for h in pools[n]) >= sb[n] / g ** length_penalty):
+                    done[n] = True
+            step += 1
+            if all(done) or step == max_new_tokens:
+                break
+            done_dev.copy_(torch.tensor(done, dtype=torch.int32))
+            scores = out["next_scores"]
+            if not indirect:                                   # the yardstick: move every layer's K and V to the beams' new rows
+                gidx = row0 + out["parent"]
+                st.k.copy_(st.k.index_select(1, gidx))
+                st.v.copy_(st.v.index_select(1, gidx))
+            st.x.copy_(ops.gather_rows(emb_w, out["next_token"]))
+            self._decode_step(st, use_graph)
+            hids.append(st.hidden.clone())
+            logits = st.logits
+        last = out["next_scores"].cpu().tolist()
+        for n in range(N):                                     # a prompt that is not done: its live beams are hypotheses of `step` tokens
+            if not done[n]:
+                for i in range(B):
+                    self._beam_pool_add(pools[n], B, (last[n * B + i] / step ** length_penalty, "live", step - 1, i))
+        tok_h, par_h = torch.stack(toks).cpu().tolist(), torch.stack(pars).cpu().tolist()      # [steps, R]
+        rows, gather, values = [], [], []
+        for n in range(N):
+            best = pools[n][0]
+            for h in pools[n][1:]:
+                if h[0] > best[0]:
+                    best = h
+            value, kind, s, slot = best
+            seq, slots = [], [None] * (s + 1)
+            if kind == "eos":
+                seq.append(int(eos_token_id))
+                s -= 1
+            while s >= 0:
+                slots[s] = slot
+                seq.append(tok_h[s][n * B + slot])
+                slot = par_h[s][n * B + slot]
+                s -= 1
+            seq.reverse()
+            rows.append(seq)
+            values.append(value)
+            gather.append([t * R + n * B + slots[t] for t in range(len(seq) - 1)])      # the state of each fed token: every token but the last
+        n_new = max(len(r) for r in rows)
+        out_ids = torch.full((N, L + n_new), fill, dtype=torch.int64)
+        out_ids[:, :L] = input_ids.cpu()
+        for n, r in enumerate(rows):
+            out_ids[n, L:L + len(r)] = torch.tensor(r, dtype=torch.int64)
+        hidden = torch.zeros((N, T + n_new - 1, H), device=dev, dtype=BF16)
+        hidden[:, :T] = hidden_p
+        if hids:
+            flat = torch.stack(hids).view(-1, H)
+            for n, gi in enumerate(gather):
+                if gi:
+                    hidden[n, T:T + len(gi)] = flat.index_select(0, torch.tensor(gi, device=dev))
+        res = (out_ids.to(dev), hidden)
+        return res + (torch.tensor(values, dtype=torch.float32, device=dev),) if return_beam_scores else res
+
+    @staticmethod
+    def _beam_pool_add(pool, B, hyp):
+        """Hugging Face's BeamHypotheses.add: keep the B best by value; a newcomer enters a full pool only when it beats the worst, which then leaves."""
+        if len(pool) < B:
+            pool.append(hyp)
+        elif hyp[0] > min(h[0] for h in pool):
+            worst = min(range(len(pool)), key=lambda i: pool[i][0])
+            pool[worst] = hyp
 
     @staticmethod
     def _ragged_prompts(input_ids, attention_mask):

@@ -349,14 +349,25 @@ def rope_kv_append_(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim):
     return qkv
 
 
-def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=None, scale=None, scratch=None, per_row=False):
+def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=None, scale=None, scratch=None, per_row=False, beam_src=None):
     """Decode step in one launch (+ merge): k rotated / v copied into the caches at position *pos_dev, out[n] = attention of the rotated q
     over the pos + 1 cached keys.  head_dim 128.  scratch: fp32 buffer from decode_attn_scratch (None = one workgroup per head).
-    per_row: pos_dev is int32 [N], sequence n rotates, appends and attends at its own position pos_dev[n] (llmseg_decode_attn_rows)."""
+    per_row: pos_dev is int32 [N], sequence n rotates, appends and attends at its own position pos_dev[n] (llmseg_decode_attn_rows).
+    beam_src (needs per_row): int32 [N, >= capacity] table, key t < pos of row n is read from physical cache row beam_src[n, t]
+    (llmseg_decode_attn_beams; entries are trusted to lie in [0, N))."""
     N = qkv.shape[0]
     assert kcache.shape == vcache.shape and kcache.shape[0] == N and kcache.stride(1) == heads * head_dim and pos_dev.dtype == torch.int32
     if out is None:
         out = torch.empty((N, heads * head_dim), device=qkv.device, dtype=torch.bfloat16)
+    if beam_src is not None:
+        assert per_row and pos_dev.numel() == N and pos_dev.is_contiguous()
+        assert beam_src.is_cuda and beam_src.dtype == torch.int32 and beam_src.dim() == 2 and beam_src.shape[0] == N and beam_src.stride(1) == 1
+        _lib.check(_lib.load().llmseg_decode_attn_beams(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(pos_dev),
+                                                        _ptr(beam_src), max(beam_src.stride(0), beam_src.shape[1]) if N == 1 else beam_src.stride(0), kcache.shape[1],
+                                                        N, heads, head_dim, float(scale if scale is not None else head_dim ** -0.5), _ptr(out), out.stride(0),
+                                                        _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,
+                                                        _stream()), "decode_attn_beams")
+        return out
     if per_row:
         assert pos_dev.numel() == N and pos_dev.is_contiguous()
         _lib.check(_lib.load().llmseg_decode_attn_rows(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(pos_dev),
@@ -368,6 +379,43 @@ def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=Non
                                               N, heads, head_dim, float(scale if scale is not None else head_dim ** -0.5), _ptr(out), out.stride(0),
                                               _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,
                                               _stream()), "decode_attn")
+    return out
+
+
+def beam_step(logits, beam_scores, done, src_in, src_out, pos_rows, num_beams, eos_token_id=None, pad_token_id=0, out=None, workspace=None):
+    """One beam-search pick (`llmseg_beam_step`, two launches; the rule and its arithmetic are stated in include/llmseg_hip.h).  logits bf16
+    [N * beams_in, V] (beams_in = 1: the first pick, else num_beams), beam_scores fp32 [N * beams_in], done int32 [N], src_in / src_out int32
+    [N * B, ld] (two different buffers), pos_rows int32 [N * B].  -> dict(next_token int64 [N * B], parent int32 [N * B], next_scores fp32 [N * B],
+    step_best fp32 [N], fin_count int32 [N], fin_parent int32 [N, B], fin_score fp32 [N, B]); `out` = such a dict to write into."""
+    _req(logits)
+    B = int(num_beams)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and done.dtype == torch.int32 and done.dim() == 1 and done.is_contiguous()
+    N, V = done.shape[0], logits.shape[1]
+    beams_in = logits.shape[0] // N
+    dev = logits.device
+    R = N * B
+    assert logits.shape[0] == N * beams_in and beam_scores.dtype == torch.float32 and beam_scores.shape == (N * beams_in,) and beam_scores.is_contiguous()
+    for t in (src_in, src_out):
+        assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == R and t.stride(1) == 1
+    assert src_in.shape == src_out.shape and src_in.stride(0) == src_out.stride(0)
+    assert pos_rows.dtype == torch.int32 and pos_rows.shape == (R,) and pos_rows.is_contiguous()
+    if out is None:
+        out = dict(next_token=torch.empty((R,), device=dev, dtype=torch.int64), parent=torch.empty((R,), device=dev, dtype=torch.int32),
+                   next_scores=torch.empty((R,), device=dev, dtype=torch.float32), step_best=torch.empty((N,), device=dev, dtype=torch.float32),
+                   fin_count=torch.empty((N,), device=dev, dtype=torch.int32), fin_parent=torch.empty((N, B), device=dev, dtype=torch.int32),
+                   fin_score=torch.empty((N, B), device=dev, dtype=torch.float32))
+    shapes = dict(next_token=((R,), torch.int64), parent=((R,), torch.int32), next_scores=((R,), torch.float32), step_best=((N,), torch.float32),
+                  fin_count=((N,), torch.int32), fin_parent=((N, B), torch.int32), fin_score=((N, B), torch.float32))
+    for k, (shp, dt) in shapes.items():
+        assert out[k].is_cuda and tuple(out[k].shape) == shp and out[k].dtype == dt and out[k].is_contiguous(), k
+    if workspace is None:
+        workspace = torch.empty((N * beams_in * 2 * B,), device=dev, dtype=torch.int64)
+    ld_src = max(src_in.stride(0), src_in.shape[1]) if R == 1 else src_in.stride(0)
+    _lib.check(_lib.load().llmseg_beam_step(_ptr(logits), max(logits.stride(0), V) if logits.shape[0] == 1 else logits.stride(0), _ptr(beam_scores), _ptr(done),
+                                            -1 if eos_token_id is None else int(eos_token_id), 0 if pad_token_id is None else int(pad_token_id), _ptr(src_in),
+                                            _ptr(src_out), ld_src, _ptr(pos_rows), N, B, beams_in, V, _ptr(out["next_token"]), _ptr(out["parent"]),
+                                            _ptr(out["next_scores"]), _ptr(out["step_best"]), _ptr(out["fin_count"]), _ptr(out["fin_parent"]), _ptr(out["fin_score"]),
+                                            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()), "beam_step")
     return out
 
 
