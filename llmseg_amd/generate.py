@@ -54,12 +54,14 @@ class DecodeState:
         self.logits = torch.empty((N, V), device=device, dtype=BF16)
         self.N, self.cap, self.H = N, cap, H
         self.graph = None
+        self.warm = False            # the state's first step ran eagerly (the step is captured at its second)
         self.fused = False           # decode step on merged-LoRA weights (+ norm / SwiGLU on the GEMM's A load for a single sequence)
         self.qkv_w = None            # per-layer q|k|v weights with the LoRA deltas merged in (fused steps)
         self.bits = None             # weight_bits of the captured step (None = bf16 weights)
         self.ragged = False          # the captured step reads pos_rows (one position per sequence) instead of pos
         self.w8 = None               # weight_bits = 8: {layer-matrix name: (q int8, scale fp32, w_hat bf16)} of `_quantize_w8`
         self.beam_src = None         # beam search over the never-moved cache: int32 [N, capacity], key t of row r lives in physical row beam_src[r, t]
+        self.src_a = self.src_b = None      # beam search: the table at a fixed address (the captured step reads it) and the buffer `ops.beam_step` re-orders it into
 
 
 class GenerateMixin:
@@ -94,82 +96,95 @@ class GenerateMixin:
     def _decode_body(self, st):
         """One token per sequence through the decoder stack: st.x (embeddings of the token at position st.pos[0]) -> st.hidden, st.logits;
         K / V of the token are appended to the cache and the position advances.  No host-visible state: the step is a pure kernel
-        sequence over fixed buffers, replayable from a hipGraph.  Six launches per layer for a single sequence (LoRA
-        merged): q|k|v GEMM with the input RMSNorm on its A load, RoPE + KV append, attention, o_proj (+ residual), gate|up GEMM with the
-        post-attention RMSNorm on its A load, down_proj (+ residual) with SwiGLU on its A load."""
+        sequence over fixed buffers, replayable from a hipGraph.  Every route is this one loop; the routes differ in how a layer's four
+        matrices are applied (`_decode_linears`) and in how attention runs (`_decode_attention`).  Six launches per layer for a single
+        sequence (LoRA merged): q|k|v GEMM with the input RMSNorm on its A load, RoPE + KV append + attention (+ the split's merge), o_proj
+        (+ residual), gate|up GEMM with the post-attention RMSNorm on its A load, down_proj (+ residual) with SwiGLU on its A load."""
         c = self.config.llama
         F = _Direct
         N, H = st.x.shape
-        if st.fused:
-            onload = N == 1      # RMSNorm / SwiGLU on the skinny GEMM's A load: every wave redoes the transform, a win for one row only (two rows: 4.02 vs
-            #                      3.90 ms per token with the norm on load, 5.97 vs 4.34 with both): more rows keep the separate launches
-            cos, sin, _ = self._rope(st.cap)
-            hd, heads = c.head_dim, c.heads
-            x = st.x
-            att = torch.empty((N, H), device=x.device, dtype=BF16)
-            scratch = ops.decode_attn_scratch(N, heads, x.device) if hd == 128 else None
-            for i in range(c.layers):
-                p = f"model.layers.{i}."
-                wq = st.qkv_w[i] if st.qkv_w is not None else self._wcat(p + "qkv", [p + f"self_attn.{n}_proj.weight" for n in "qkv"], F)
-                if onload:
-                    qkv = ops.gemm(x, wq, a_norm_w=self._w(p + "input_layernorm.weight", F), a_norm_eps=c.eps)
-                else:
-                    qkv = ops.gemm(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), wq)
-                if hd == 128:                                  # RoPE + KV append + attention over the cache: one launch (+ the split's merge)
-                    if st.ragged:                              # every sequence at its own position: RoPE angle, cache slot and key count
-                        ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True, beam_src=st.beam_src)
-                    else:
-                        ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
-                else:
-                    ld = qkv.stride(0)
-                    ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)
-                    ops.attention(qkv, st.k[i], st.v[i], att, batch=N, heads=heads, Nq=1, Nk=st.cap, head_dim=hd, q_strides=(ld, hd, ld),
-                                  k_strides=(st.cap * H, hd, H), v_strides=(st.cap * H, hd, H), o_strides=(H, hd, H), nk_dev=st.pos[1:])
-                x = ops.gemm(att, self._w(p + "self_attn.o_proj.weight", F), residual=x)
-                wgu = self._wcat(p + "gate_up", [p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], F)
-                if onload:
-                    gu = ops.gemm(x, wgu, a_norm_w=self._w(p + "post_attention_layernorm.weight", F), a_norm_eps=c.eps)
-                else:
-                    gu = ops.gemm(F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True), wgu)
-                if onload:
-                    x = ops.gemm(gu, self._w(p + "mlp.down_proj.weight", F), residual=x, a_swiglu=True)
-                else:
-                    x = ops.gemm(ops.swiglu(gu, c.inter), self._w(p + "mlp.down_proj.weight", F), residual=x)
-            ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
-            ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)
-            (st.pos_rows if st.ragged else st.pos).add_(1)
-            return
+        lin = self._decode_linears(st)
         cos, sin, _ = self._rope(st.cap)
-        s = c.lora_alpha / c.lora_r if c.lora_r > 0 else 0.0
-        hd, heads = c.head_dim, c.heads
         x = st.x
         att = torch.empty((N, H), device=x.device, dtype=BF16)
+        scratch = ops.decode_attn_scratch(N, c.heads, x.device) if st.fused and c.head_dim == 128 else None
         for i in range(c.layers):
-            p = f"model.layers.{i}."
-            h = F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True)
-            qkv = ops.gemm(h, self._wcat(p + "qkv", [p + f"self_attn.{n}_proj.weight" for n in "qkv"], F))      # skinny GEMM: a weight stream
-            if c.lora_r > 0:
+            qkv = lin(i, "qkv", x, norm="input_layernorm.weight")
+            self._decode_attention(st, i, qkv, cos, sin, att, scratch)
+            x = lin(i, "self_attn.o_proj.weight", att, residual=x)
+            gu = lin(i, "gate_up", x, norm="post_attention_layernorm.weight")
+            x = lin(i, "mlp.down_proj.weight", gu, swiglu=True, residual=x)
+        ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
+        ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)          # lm_head stays bf16 at weight_bits = 8 too: 2 % of the stream, and it decides the arg-max
+        (st.pos_rows if st.ragged else st.pos).add_(1)
+
+    def _decode_attention(self, st, i, qkv, cos, sin, att, scratch):
+        """RoPE of the new token's q and k at the device-side position, its K / V appended to layer i's cache, attention of the one query over the cache -> att."""
+        c = self.config.llama
+        hd, heads, H = c.head_dim, c.heads, st.H
+        if st.fused and hd == 128:                             # one launch (+ the split's merge); ragged: every sequence at its own position (RoPE angle, cache slot, key count)
+            ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows if st.ragged else st.pos, heads, hd, out=att, scratch=scratch, per_row=st.ragged,
+                            beam_src=st.beam_src)
+        else:
+            ld = qkv.stride(0)
+            ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)       # q, k rotated at the device-side position; k, v -> cache
+            ops.attention(qkv, st.k[i], st.v[i], att, batch=st.N, heads=heads, Nq=1, Nk=st.cap, head_dim=hd, q_strides=(ld, hd, ld),
+                          k_strides=(st.cap * H, hd, H), v_strides=(st.cap * H, hd, H), o_strides=(H, hd, H), nk_dev=st.pos[1:])
+
+    def _decode_linears(self, st):
+        """How a decode step applies a layer's four matrices (W8_MATRICES) on this state's route, chosen once per step:
+        -> lin(i, name, a, norm=None, swiglu=False, residual=None) = f(a) @ W_name^T (+ residual) of layer i, f = the RMSNorm of weight `norm`, SwiGLU, or nothing."""
+        c = self.config.llama
+        F = _Direct
+        H = st.H
+        prefix = "model.layers.{}.".format
+
+        def pre(p, a, norm, swiglu):                           # f as a launch of its own
+            if norm is not None:
+                return F.norm(a, self._w(p + norm, F), None, c.eps, True)
+            return ops.swiglu(a, c.inter) if swiglu else a
+
+        if st.bits is not None:                                # int8 rows; the A-load fusions of the bf16 route for a single sequence are not built for this kernel
+            def lin_w8(i, name, a, norm=None, swiglu=False, residual=None):
+                p = prefix(i)
+                return self._gemm_w8_rows(pre(p, a, norm, swiglu), *st.w8[p + name][:2], residual=residual)
+            return lin_w8
+
+        members = {"qkv": [f"self_attn.{n}_proj.weight" for n in "qkv"], "gate_up": ["mlp.gate_proj.weight", "mlp.up_proj.weight"]}
+
+        def weight(i, p, name):                                # bf16: q|k|v with the LoRA deltas merged in where the step is fused
+            if name == "qkv" and st.qkv_w is not None:
+                return st.qkv_w[i]
+            return self._wcat(p + name, [p + m for m in members[name]], F) if name in members else self._w(p + name, F)
+
+        onload = st.fused and st.N == 1      # RMSNorm / SwiGLU on the skinny GEMM's A load: every wave redoes the transform, a win for one row only (two rows: 4.02 vs
+        #                                      3.90 ms per token with the norm on load, 5.97 vs 4.34 with both): more rows keep the separate launches
+        if onload:
+            def lin_onload(i, name, a, norm=None, swiglu=False, residual=None):
+                p = prefix(i)
+                return ops.gemm(a, weight(i, p, name), residual=residual, a_norm_w=None if norm is None else self._w(p + norm, F), a_norm_eps=c.eps, a_swiglu=swiglu)
+            return lin_onload
+
+        lora = not st.fused and c.lora_r > 0                   # fuse_decode=False: the LoRA deltas of q and v as launches of their own
+        s = c.lora_alpha / c.lora_r if lora else 0.0
+
+        def lin(i, name, a, norm=None, swiglu=False, residual=None):
+            p = prefix(i)
+            h = pre(p, a, norm, swiglu)
+            out = ops.gemm(h, weight(i, p, name), residual=residual)      # skinny GEMM: a weight stream
+            if lora and name == "qkv":
                 lp = p + "self_attn."
                 aq, bq = self._w(lp + "q_proj.lora_A.default.weight", F), self._w(lp + "q_proj.lora_B.default.weight", F)
                 av, bv = self._w(lp + "v_proj.lora_A.default.weight", F), self._w(lp + "v_proj.lora_B.default.weight", F)
                 if c.lora_r == 8:                              # rank-8 kernels: [h Aq^T | h Av^T] in one pass, then the two rank-8 updates
                     xa = ops.lora_down(h, aq, x2=h, w2=av)
-                    ops.lora_apply_(qkv[:, :H], xa, bq, alpha=s)
-                    ops.lora_apply_(qkv[:, 2 * H:], xa[:, 8:], bv, alpha=s)
+                    ops.lora_apply_(out[:, :H], xa, bq, alpha=s)
+                    ops.lora_apply_(out[:, 2 * H:], xa[:, 8:], bv, alpha=s)
                 else:
-                    ops.gemm(ops.gemm(h, aq), bq, residual=qkv[:, :H], out=qkv[:, :H], alpha=s)
-                    ops.gemm(ops.gemm(h, av), bv, residual=qkv[:, 2 * H:], out=qkv[:, 2 * H:], alpha=s)
-            ld = qkv.stride(0)
-            ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)       # q, k rotated at the device-side position; k, v -> cache
-            ops.attention(qkv, st.k[i], st.v[i], att, batch=N, heads=heads, Nq=1, Nk=st.cap, head_dim=hd, q_strides=(ld, hd, ld),
-                          k_strides=(st.cap * H, hd, H), v_strides=(st.cap * H, hd, H), o_strides=(H, hd, H), nk_dev=st.pos[1:])
-            x = ops.gemm(att, self._w(p + "self_attn.o_proj.weight", F), residual=x)
-            h = F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True)
-            gu = ops.gemm(h, self._wcat(p + "gate_up", [p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], F))
-            x = ops.gemm(ops.swiglu(gu, c.inter), self._w(p + "mlp.down_proj.weight", F), residual=x)
-        ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
-        ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)
-        st.pos.add_(1)
+                    ops.gemm(ops.gemm(h, aq), bq, residual=out[:, :H], out=out[:, :H], alpha=s)
+                    ops.gemm(ops.gemm(h, av), bv, residual=out[:, 2 * H:], out=out[:, 2 * H:], alpha=s)
+            return out
+        return lin
 
     W8_MATRICES = ("qkv", "self_attn.o_proj.weight", "gate_up", "mlp.down_proj.weight")      # per layer, under "model.layers.{i}."
 
@@ -232,38 +247,6 @@ class GenerateMixin:
             x = ops.gemm(ops.swiglu(gu, c.inter), w8[p + "mlp.down_proj.weight"][2], residual=x)
         return F.norm(x, self._w("model.norm.weight", F), None, c.eps, True).view(N, T, H)
 
-    def _decode_body_w8(self, st):
-        """`_decode_body`'s fused step with `ops.gemm_w8` on the int8 rows in place of its four GEMMs; RMSNorm and SwiGLU are the separate
-        launches at every N (the A-load fusions of the bf16 route for a single sequence are not built for this kernel)."""
-        c = self.config.llama
-        F = _Direct
-        N, H = st.x.shape
-        cos, sin, _ = self._rope(st.cap)
-        hd, heads = c.head_dim, c.heads
-        x = st.x
-        att = torch.empty((N, H), device=x.device, dtype=BF16)
-        scratch = ops.decode_attn_scratch(N, heads, x.device) if hd == 128 else None
-        for i in range(c.layers):
-            p = f"model.layers.{i}."
-            q8 = lambda name: st.w8[p + name][:2]
-            qkv = self._gemm_w8_rows(F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True), *q8("qkv"))
-            if hd == 128:                                  # RoPE + KV append + attention over the cache: one launch (+ the split's merge)
-                if st.ragged:
-                    ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, out=att, scratch=scratch, per_row=True, beam_src=st.beam_src)
-                else:
-                    ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd, out=att, scratch=scratch)
-            else:
-                ld = qkv.stride(0)
-                ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)
-                ops.attention(qkv, st.k[i], st.v[i], att, batch=N, heads=heads, Nq=1, Nk=st.cap, head_dim=hd, q_strides=(ld, hd, ld),
-                              k_strides=(st.cap * H, hd, H), v_strides=(st.cap * H, hd, H), o_strides=(H, hd, H), nk_dev=st.pos[1:])
-            x = self._gemm_w8_rows(att, *q8("self_attn.o_proj.weight"), residual=x)
-            gu = self._gemm_w8_rows(F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True), *q8("gate_up"))
-            x = self._gemm_w8_rows(ops.swiglu(gu, c.inter), *q8("mlp.down_proj.weight"), residual=x)
-        ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
-        ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)          # lm_head stays bf16: 2 % of the stream, and it decides the arg-max
-        (st.pos_rows if st.ragged else st.pos).add_(1)
-
     @staticmethod
     def _gemm_w8_rows(a, q, scale, residual=None):
         """`ops.gemm_w8` (at most 8 rows a call) on any number of rows: up to 8 rows it IS that call; more rows (prompts x beams) go in chunks of 8, each
@@ -279,18 +262,58 @@ class GenerateMixin:
     def _decode_step(self, st, use_graph=True):
         """Run one decode step; from the second step of a state on, replay it from a hipGraph (captured once per (N, capacity): a step is
         ~420 launches of 5-20 us kernels, the host cannot issue them as fast as the GPU finishes them)."""
-        body = self._decode_body if st.bits is None else self._decode_body_w8
         if not use_graph:
-            return body(st)
+            return self._decode_body(st)
         if st.graph is None:
-            if not getattr(st, "warm", False):
+            if not st.warm:
                 st.warm = True
-                return body(st)                                 # first step of this state: eager (also warms every allocation)
+                return self._decode_body(st)                    # first step of this state: eager (also warms every allocation)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):      # (another thread -- an RCCL watchdog -- may query events meanwhile: train.py::_capture)
-                body(st)
+                self._decode_body(st)
             st.graph = g                                        # capture records, it does not execute: fall through to the replay
         st.graph.replay()
+
+    def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, weight_bits, fused, key):
+        """What every generate() route does before its loop: the prompts (input_ids [N, L], trimmed; attention_mask = the ragged call's mask, else None) through
+        the prefill, K and V of prompt n into physical row n * rows of the decode state of N * rows rows (rows = 1, or the beams per prompt), the state made ready
+        for the call's route.  The states are kept per (N * rows, capacity) + key.  -> (state, final-norm hidden [N, T, H], T, embedding weights, lm_head weights)."""
+        self.prepare()
+        c = self.config
+        cl = c.llama
+        dev = self.device_
+        F = _Direct
+        N, L = input_ids.shape
+        Pn, H = c.n_img_tokens, cl.hidden
+        T = L - 1 + Pn
+        assert max_new_tokens >= 1
+        plan = self.make_plan(input_ids, None, torch.ones((N, L), dtype=torch.bool) if attention_mask is None else attention_mask, list(range(N + 1)), None, inference=False)
+        proj = self.encode_images(images_clip.to(dev, BF16))
+        emb_w = self._w("model.embed_tokens.weight", F)
+        embeds = F.embed_splice(input_ids.to(dev).contiguous(), emb_w, proj[1:], Pn, (Pn + 1) * H, plan.tok_index)
+        cap = (T + max_new_tokens + 63) // 64 * 64
+        states = self.__dict__.setdefault("_decode_states", {})
+        st = states.get((N * rows, cap) + key)
+        if st is None:
+            st = states[(N * rows, cap) + key] = DecodeState(cl.layers, N * rows, cap, H, cl.vocab, dev)
+
+        # ragged prompts: K and V are copied for [:, :T] of every row.  The slots at or beyond a row's own T_i = L_i - 1 + Pn then hold the padding's
+        # K / V (and, past T, whatever an earlier call left): garbage that is never read, because the step that feeds a row's token at position
+        # pos writes cache[pos] itself and attends to keys 0 .. pos only -- a slot is overwritten before the row's key count reaches it.
+        def keep_kv(i, qkv):                                   # qkv [N*T, 3H] after the in-place RoPE of q and k
+            st.k[i, ::rows, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
+            st.v[i, ::rows, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
+        if weight_bits is None:
+            st.w8 = None
+            hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
+        else:
+            st.w8 = self._quantize_w8()
+            hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
+        ragged = attention_mask is not None or rows > 1       # beams: every row at its own device-side position (they are equal; the per-row kernels read them)
+        if fused != st.fused or weight_bits != st.bits or ragged != st.ragged:
+            st.fused, st.bits, st.ragged, st.graph, st.warm = fused, weight_bits, ragged, None, False      # a different kernel sequence: capture again
+        st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0 and weight_bits is None) else None
+        return st, hidden_p, T, emb_w, self._w("lm_head.weight", F)
 
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
@@ -382,53 +405,22 @@ class GenerateMixin:
                 raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
             return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, weight_bits, attention_mask, num_beams,
                                         float(length_penalty), early_stopping, return_beam_scores, beam_cache, _beam_trace)
-        self.prepare()
-        c = self.config
-        cl = c.llama
-        dev = self.device_
         lens = None                                            # prompt lengths L_i on the host, ragged calls only
         if attention_mask is not None:
             input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
         if lens is not None:
             if not fuse_decode:
                 raise ValueError("prompts of different lengths need fuse_decode=True (the per-row positions are built into the fused decode step only)")
-            if cl.head_dim != 128:
-                raise ValueError(f"prompts of different lengths need head_dim 128, got {cl.head_dim}: per-row key counts for the two-launch "
+            if self.config.llama.head_dim != 128:
+                raise ValueError(f"prompts of different lengths need head_dim 128, got {self.config.llama.head_dim}: per-row key counts for the two-launch "
                                  "route (llmseg_rope_kv_append + llmseg_attn_fwd) are out of scope")
             fill = 0 if pad_token_id is None else int(pad_token_id)
             input_ids = torch.where(attention_mask.to(input_ids.device), input_ids, torch.full_like(input_ids, fill))
-        N, L = input_ids.shape
-        Pn, H = c.n_img_tokens, cl.hidden
-        T = L - 1 + Pn
-        assert max_new_tokens >= 1
-        plan = self.make_plan(input_ids, None, torch.ones((N, L), dtype=torch.bool) if lens is None else attention_mask, list(range(N + 1)), None, inference=False)
-        F = _Direct
-        proj = self.encode_images(images_clip.to(dev, BF16))
-        embeds = F.embed_splice(input_ids.to(dev).contiguous(), self._w("model.embed_tokens.weight", F), proj[1:], Pn, (Pn + 1) * H, plan.tok_index)
-        cap = (T + max_new_tokens + 63) // 64 * 64
-        states = self.__dict__.setdefault("_decode_states", {})
-        st = states.get((N, cap))
-        if st is None:
-            st = states[(N, cap)] = DecodeState(cl.layers, N, cap, H, cl.vocab, dev)
-
-        # ragged prompts: K and V are copied for [:, :T] of every row.  The slots at or beyond a row's own T_i = L_i - 1 + Pn then hold the padding's
-        # K / V (and, past T, whatever an earlier call left): garbage that is never read, because the step that feeds a row's token at position
-        # pos writes cache[pos] itself and attends to keys 0 .. pos only -- a slot is overwritten before the row's key count reaches it.
-        def keep_kv(i, qkv):                                   # qkv [N*T, 3H] after the in-place RoPE of q and k
-            st.k[i, :, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
-            st.v[i, :, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
-        if weight_bits is None:
-            st.w8 = None
-            hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
-        else:
-            st.w8 = self._quantize_w8()
-            hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
-        fused = bool(fuse_decode)
         ragged = lens is not None
-        if fused != st.fused or weight_bits != st.bits or ragged != st.ragged:
-            st.fused, st.bits, st.ragged, st.graph, st.warm = fused, weight_bits, ragged, None, False      # a different kernel sequence: capture again
-        st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0 and weight_bits is None) else None
-        emb_w = self._w("model.embed_tokens.weight", F)
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, weight_bits, bool(fuse_decode), ())
+        dev = self.device_
+        N, L = input_ids.shape
+        Pn, H = self.config.n_img_tokens, self.config.llama.hidden
         if ragged:
             t_rows = (lens - 1 + Pn).to(dev)                    # T_i: row i's prefill length = the position of its first fed token
             st.pos_rows.copy_(t_rows.to(torch.int32))
@@ -436,13 +428,13 @@ class GenerateMixin:
             own = torch.arange(T, device=dev)[None, :] < t_rows[:, None]
             hidden[:, :T] = torch.where(own[:, :, None], hidden_p, torch.zeros_like(hidden_p))
             last = torch.arange(N, device=dev) * T + t_rows - 1                            # each row's own last prompt position
-            logits = ops.gemm(ops.gather_rows(hidden_p.reshape(N * T, H), last), self._w("lm_head.weight", F))
+            logits = ops.gemm(ops.gather_rows(hidden_p.reshape(N * T, H), last), lm_w)
             slot = torch.arange(N, device=dev) * hidden.shape[1] + t_rows - 1                # flat row of `hidden` that holds each sequence's newest state
         else:
             st.pos.copy_(torch.tensor([T, T + 1], dtype=torch.int32))
             hidden = torch.empty((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
             hidden[:, :T] = hidden_p
-            logits = ops.gemm(hidden_p[:, -1].contiguous(), self._w("lm_head.weight", F))     # only the last position's logits are needed
+            logits = ops.gemm(hidden_p[:, -1].contiguous(), lm_w)     # only the last position's logits are needed
         seqs = [input_ids.to(dev)]
         unfinished = torch.ones((N,), dtype=torch.int64, device=dev)
         n_new = 0
@@ -493,47 +485,20 @@ class GenerateMixin:
             input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
             if lens is not None:
                 raise ValueError("num_beams >= 2 with prompts of different lengths (an attention_mask that is ragged after trimming) is out of scope")
-        self.prepare()
-        c = self.config
-        cl = c.llama
+        indirect = beam_cache == "indirect"
+        # a state of its own: a greedy call on N * B sequences never meets a beam call's graph
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, None, B, max_new_tokens, weight_bits, True, ("beams", beam_cache))
         dev = self.device_
         N, L = input_ids.shape
-        R = N * B
-        Pn, H = c.n_img_tokens, cl.hidden
-        T = L - 1 + Pn
-        assert max_new_tokens >= 1
+        R, H = N * B, self.config.llama.hidden
         fill = 0 if pad_token_id is None else int(pad_token_id)
-        plan = self.make_plan(input_ids, None, torch.ones((N, L), dtype=torch.bool), list(range(N + 1)), None, inference=False)
-        F = _Direct
-        proj = self.encode_images(images_clip.to(dev, BF16))
-        embeds = F.embed_splice(input_ids.to(dev).contiguous(), self._w("model.embed_tokens.weight", F), proj[1:], Pn, (Pn + 1) * H, plan.tok_index)
-        cap = (T + max_new_tokens + 63) // 64 * 64
-        indirect = beam_cache == "indirect"
-        states = self.__dict__.setdefault("_decode_states", {})
-        st = states.get((R, cap, "beams", beam_cache))         # a state of its own: a greedy call on R sequences never meets a beam call's graph
-        if st is None:
-            st = states[(R, cap, "beams", beam_cache)] = DecodeState(cl.layers, R, cap, H, cl.vocab, dev)
-            st.fused, st.ragged = True, True                   # every row at its own device-side position (they are equal; the per-row kernels read them)
-            st.src_a = torch.zeros((R, cap), device=dev, dtype=torch.int32)      # the table, at a fixed address: the captured step reads it
-            st.src_b = torch.zeros((R, cap), device=dev, dtype=torch.int32)      # ... and the buffer `ops.beam_step` writes the re-ordered table to (copied back)
+        if st.src_a is None:                                   # a new state
+            st.src_a = torch.zeros((R, st.cap), device=dev, dtype=torch.int32)
+            st.src_b = torch.zeros((R, st.cap), device=dev, dtype=torch.int32)
             if indirect:
                 st.beam_src = st.src_a
-
-        def keep_kv(i, qkv):                                   # the prompt's K and V once per prompt: physical row n * B
-            st.k[i, ::B, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
-            st.v[i, ::B, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
-        if weight_bits is None:
-            st.w8 = None
-            hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
-        else:
-            st.w8 = self._quantize_w8()
-            hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
-        if weight_bits != st.bits:
-            st.bits, st.graph, st.warm = weight_bits, None, False
-        st.qkv_w = self._merge_lora() if (cl.lora_r > 0 and weight_bits is None) else None
-        emb_w = self._w("model.embed_tokens.weight", F)
         st.pos_rows.fill_(T)
-        logits = ops.gemm(hidden_p[:, -1].contiguous(), self._w("lm_head.weight", F))      # [N, V]: the first pick reads one row per prompt
+        logits = ops.gemm(hidden_p[:, -1].contiguous(), lm_w)      # [N, V]: the first pick reads one row per prompt
         scores = torch.zeros((N,), device=dev, dtype=torch.float32)
         done_dev = torch.zeros((N,), device=dev, dtype=torch.int32)
         # the pick's small outputs in ONE buffer, so that one copy brings them to the host: step_best [N] | fin_count [N] | fin_parent [N, B] | fin_score [N, B]

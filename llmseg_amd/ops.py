@@ -359,26 +359,16 @@ def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=Non
     assert kcache.shape == vcache.shape and kcache.shape[0] == N and kcache.stride(1) == heads * head_dim and pos_dev.dtype == torch.int32
     if out is None:
         out = torch.empty((N, heads * head_dim), device=qkv.device, dtype=torch.bfloat16)
-    if beam_src is not None:
+    name, extra = "decode_attn_rows" if per_row else "decode_attn", ()
+    if per_row or beam_src is not None:
         assert per_row and pos_dev.numel() == N and pos_dev.is_contiguous()
+    if beam_src is not None:
         assert beam_src.is_cuda and beam_src.dtype == torch.int32 and beam_src.dim() == 2 and beam_src.shape[0] == N and beam_src.stride(1) == 1
-        _lib.check(_lib.load().llmseg_decode_attn_beams(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(pos_dev),
-                                                        _ptr(beam_src), max(beam_src.stride(0), beam_src.shape[1]) if N == 1 else beam_src.stride(0), kcache.shape[1],
-                                                        N, heads, head_dim, float(scale if scale is not None else head_dim ** -0.5), _ptr(out), out.stride(0),
-                                                        _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,
-                                                        _stream()), "decode_attn_beams")
-        return out
-    if per_row:
-        assert pos_dev.numel() == N and pos_dev.is_contiguous()
-        _lib.check(_lib.load().llmseg_decode_attn_rows(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(pos_dev),
+        name, extra = "decode_attn_beams", (_ptr(beam_src), max(beam_src.stride(0), beam_src.shape[1]) if N == 1 else beam_src.stride(0), kcache.shape[1])
+    _lib.check(getattr(_lib.load(), "llmseg_" + name)(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(pos_dev), *extra,
                                                        N, heads, head_dim, float(scale if scale is not None else head_dim ** -0.5), _ptr(out), out.stride(0),
                                                        _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,
-                                                       _stream()), "decode_attn_rows")
-        return out
-    _lib.check(_lib.load().llmseg_decode_attn(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(pos_dev),
-                                              N, heads, head_dim, float(scale if scale is not None else head_dim ** -0.5), _ptr(out), out.stride(0),
-                                              _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,
-                                              _stream()), "decode_attn")
+                                                       _stream()), name)
     return out
 
 

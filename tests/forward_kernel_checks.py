@@ -1,4 +1,4 @@
-"""Forward glue, decode and head kernels (llmseg_amd/csrc/pointwise.hip, decode_attn of attention.hip, the pull-back, cosine and dice / BCE kernels of head.hip) on every dispatch route: a case
+"""Forward glue, decode and head kernels (llmseg_amd/csrc/pointwise.hip, decode_attn.hip, the pull-back, cosine and dice / BCE kernels of head.hip) on every dispatch route: a case
 table, input builders, fp64 references, LOCAL tolerances, fp32 / bf16 emulations of what the kernels round, and mutants (fp64 results of subtly
 wrong problems) that the tolerances must reject.
 
