@@ -479,7 +479,7 @@ int llmseg_cosine_scores(const void* t, const void* e, float* sim, int32_t K, in
 
 /* ---- ABI 7: the mask-selection head with fp32 ACTIVATIONS (inference scores; weights stay the model's bf16 tensors) ------------------------
  * What these replace on the reference side: the nn.Linear / nn.LayerNorm / Attention modules of model/transformer.py:215-341 and the scoring of
- * model/LISA.py:340-408 when the reference is run in fp32 on the CPU (its own "CPU path" of north_star).  Plain fp32 FMA chains, ascending k. */
+ * model/LISA.py:340-408 when the reference is run in fp32 on the CPU (its own "CPU path" of north_star).  Plain fp32 FMA chains, ascending k (linear_f32: one chain per K step of 16, the steps' sums added in order). */
 /* y[m][n] = act(alpha * sum_k x[m][k] * W(n,k) + bias[n]) + residual[m][n];  x fp32 [M][ldx], residual fp32 [M][ldr] or NULL, y fp32 [M][ldy];
  * W bf16: w_kn = 0 -> stored [N][ldw] (nn.Linear weight, F.linear); w_kn = 1 -> stored [K][ldw] (right operand given K-major: the channels-last
  * feature map of the mask pooling, LISA.py:201-218); bias bf16 [N] or NULL. */

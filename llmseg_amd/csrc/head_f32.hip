@@ -22,7 +22,8 @@ __device__ __forceinline__ float act_f32(float v, int act) {
 
 // y[m][n] = act(alpha * sum_k x[m][k] * W(n, k) + bias[n]) + res[m][n];  x, res, y fp32; W, bias bf16.
 // W_KN = false: W stored [N][K] (an nn.Linear weight); true: W stored [K][N] (a channels-last feature map as the right operand of the mask pooling).
-// 64 x 64 output tile per 256-thread workgroup, 4 x 4 outputs per thread, K in steps of 16 through LDS; every output is one FMA chain in ascending k.
+// 64 x 64 output tile per 256-thread workgroup, 4 x 4 outputs per thread, K in steps of 16 through LDS; every output is a two-level sum: one FMA chain in ascending k per
+// K step, the steps' partial sums added in ascending order (the blocked summation of a host BLAS, in a fixed order).
 constexpr int LT = 64, LK = 16;
 template <bool W_KN>
 __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict__ x, long ldx, const bf16_t* __restrict__ W, long ldw, const bf16_t* __restrict__ bias,
@@ -65,6 +66,11 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
       }
     }
     __syncthreads();
+    float part[4][4];   // this K step's 16 terms as a chain of their own, added to the total once: the error of a long K grows as sqrt(K / 16), not sqrt(K)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) part[i][j] = 0.f;
 #pragma unroll
     for (int kk = 0; kk < LK; ++kk) {
       float a[4], b[4];
@@ -75,8 +81,12 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+        for (int j = 0; j < 4; ++j) part[i][j] = fmaf(a[i], b[j], part[i][j]);
     }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] += part[i][j];
     __syncthreads();
   }
 #pragma unroll

@@ -1026,14 +1026,15 @@ def linear_f32(x, w, bias=None, act=ACT_NONE, residual=None, w_kn=False, alpha=1
     """act(alpha * x @ W^T + bias) + residual with fp32 activations: x fp32 [M, K] (last dim contiguous), w bf16 [N, K] (or [K, N] when w_kn),
     bias bf16 [N], residual fp32 [M, N] -> fp32 [M, N]."""
     _req(x, F32); _req(w)
-    assert x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.stride(1) == 1
+    unit = lambda t: t.shape[1] == 1 or t.stride(1) == 1            # a single column has no column stride to speak of (torch reports any)
+    assert x.dim() == 2 and w.dim() == 2 and unit(x) and unit(w)
     M, K = x.shape
     N = w.shape[1] if w_kn else w.shape[0]
     assert (w.shape[0] if w_kn else w.shape[1]) == K, (x.shape, w.shape, w_kn)
     if bias is not None:
         _req(bias); assert bias.numel() == N and bias.is_contiguous()
     if residual is not None:
-        _req(residual, F32); assert residual.shape == (M, N) and residual.stride(1) == 1
+        _req(residual, F32); assert residual.shape == (M, N) and unit(residual)
     y = torch.empty((M, N), device=x.device, dtype=F32)
     _lib.check(_lib.load().llmseg_linear_f32(_ptr(x), x.stride(0), _ptr(w), w.stride(0), 1 if w_kn else 0, _ptr(bias), _ptr(residual),
                                              residual.stride(0) if residual is not None else 0, _ptr(y), N, M, N, K, act, float(alpha), _stream()), "linear_f32")
@@ -1048,10 +1049,21 @@ def layernorm_f32(x, w, b=None, eps=1e-5):
     return y
 
 
+def strided_view_fits(t, strides, batch, heads, rows, head_dim):
+    """True when the (batch, head, row) strided view of `head_dim` contiguous columns that starts at t's first element lies inside t's storage:
+    no negative stride, and the last element it reaches is allocated."""
+    sb, sh, sr = (int(s) for s in strides)
+    last = t.storage_offset() + (batch - 1) * sb + (heads - 1) * sh + (rows - 1) * sr + head_dim - 1
+    return min(sb, sh, sr, batch, heads, rows, head_dim) >= 0 and last < t.untyped_storage().nbytes() // t.element_size()
+
+
 def attention_f32(q, k, v, o, batch, heads, Nq, Nk, head_dim, q_strides, k_strides, v_strides, o_strides, scale=None):
     """softmax(q k^T * scale) v, all operands fp32; *_strides = (batch, head, row) in elements."""
     for t in (q, k, v, o):
         _req(t, F32)
+    for name, t, st, rows in (("q", q, q_strides, Nq), ("k", k, k_strides, Nk), ("v", v, v_strides, Nk), ("o", o, o_strides, Nq)):
+        assert len(st) == 3 and strided_view_fits(t, st, batch, heads, rows, head_dim), \
+            f"attention_f32: the {name} view (strides {tuple(st)}, {batch} x {heads} x {rows} x {head_dim}) leaves its tensor's storage"
     st = (C.c_int64 * 12)(*[int(s) for tup in (q_strides, k_strides, v_strides, o_strides) for s in tup])
     _lib.check(_lib.load().llmseg_attn_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(o), st, batch, heads, Nq, Nk, head_dim,
                                            float(scale if scale is not None else 1.0 / math.sqrt(head_dim)), _stream()), "attn_f32")
