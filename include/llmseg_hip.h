@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args, 5 = llmseg_lora_down_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (19: llmseg_quantize_rows_mxfp4, llmseg_gemm_mxfp4 and llmseg_gemm_mxfp4_args; 18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 18
+#define LLMSEG_ABI_VERSION 19
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -165,6 +165,45 @@ typedef struct {
   int32_t out_f32; int32_t reserved1;
 } llmseg_gemm_w8_args;
 int llmseg_gemm_w8(const llmseg_gemm_w8_args* args, void* stream);
+
+/* ---- MXFP4 weight-only decode (OCP Microscaling: 4-bit E2M1 elements, one E8M0 scale per block of 32) ------------------------------
+ * 4.25 bits per weight: a quarter of the bf16 stream.  The dequantised weight w_hat = element * 2^e has one mantissa bit, so it is
+ * exact in bf16 and a * w_hat is exact in fp32: the model the decode steps run is exactly the one whose matrices are w_hat.  The
+ * stored bytes are the operand layout of the block-scaled MFMA forms (v_mfma_scale_f32_*_f8f6f4).
+ *
+ * llmseg_quantize_rows_mxfp4: per row n of w [N][ldw] bf16 (finite values) and per block b of 32 consecutive columns (K % 32 == 0):
+ *   amax = the largest |w| of the block;
+ *   e = the smallest integer >= -127 with amax <= 6 * 2^e (amax == 0: e = -127); scale[n][b] = e + 127, one E8M0 byte.  A finite
+ *     bf16 never needs e > 126: nothing saturates.  For a normal amax = m * 2^E, m in [1, 2): e = E - 2 when m <= 1.5, else E - 1
+ *     (integer work on the bf16 bits, no division and no logarithm);
+ *   x = w / 2^e (exact); |x| is rounded to the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6} = magnitude codes 0 .. 7, a tie going to the
+ *     EVEN code: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4;
+ *   the 4-bit code is sign << 3 | magnitude, the sign cleared when the magnitude code is 0 (-0 is never stored);
+ *   byte j of packed row n holds element 2 j in its LOW nibble and element 2 j + 1 in its HIGH nibble: packed uint8 [N][ldq];
+ *   w_hat[n][k] = bf16(element * 2^e), bf16 [N][ldh], exact whenever the result is a normal bf16; written in the same pass when
+ *     w_hat != NULL (the prefill's operand costs no extra read of w).
+ * ldq is in bytes, >= K / 2 and % 16 == 0; lds >= K / 32; ldw >= K, ldh >= K, both % 8 == 0; w, packed and w_hat 16-byte aligned.
+ * One launch; the argument checks come before it. */
+int llmseg_quantize_rows_mxfp4(const void* w, int64_t ldw, int64_t N, int64_t K, void* packed, int64_t ldq, void* scale, int64_t lds,
+                               void* w_hat /* nullable */, int64_t ldh, void* stream);
+/* llmseg_gemm_mxfp4: C[m][n] = residual[m][n] + sum_k A[m][k] * w_hat[n][k], 1 <= M <= 8 (one token per sequence), with
+ * w_hat[n][k] = element(Q[n][k / 2] nibble k % 2) * 2^(scale[n][k / 32] - 127) decoded on the fly (a block
+ * of scale byte 0 -- what the quantiser writes below 6 * 2^-127, the all-zero block among them -- holds w_hat below the fp32 normal range, which may be flushed to zero).
+ * A bf16 [M][lda]; Q uint8 [N][ldq] (ldq in bytes); scale uint8 [N][lds]; fp32 FMA accumulation of exact products; C bf16 or fp32
+ * (out_f32; ldc in elements of the output type).  K % 32 == 0, lda % 8 == 0, ldq >= K / 2 and % 16 == 0, lds >= K / 32, A and Q
+ * 16-byte aligned.  One launch (a vector-ALU weight stream at 1-2 rows, w_hat as the bf16 operand of the matrix cores from 3 rows: the products are exact
+ * either way), no atomics: same inputs, same bits. */
+typedef struct {
+  uint32_t struct_size;  /* = sizeof(llmseg_gemm_mxfp4_args) of the caller's declaration (ABI guard, see above) */
+  uint32_t reserved0;    /* 0 */
+  const void* A; const void* Q; const void* scale;
+  const void* residual;  /* bf16 [M][ldr] or NULL */
+  void* C;
+  int64_t M, N, K;
+  int64_t lda, ldq, lds, ldc, ldr;
+  int32_t out_f32; int32_t reserved1;
+} llmseg_gemm_mxfp4_args;
+int llmseg_gemm_mxfp4(const llmseg_gemm_mxfp4_args* args, void* stream);
 
 /* ---- sampling (generate(do_sample=True)): temperature, top-k, top-p, the draw, the eos rule: ONE launch ----
  * Per row n of logits [N][ldl] bf16, with temperature T > 0, top_k k >= 0 (0 = off), top_p p in (0, 1] (1 = off) and a uniform u[n] in [0, 1),

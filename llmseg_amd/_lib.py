@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 18         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 19         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
 NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
@@ -48,6 +48,12 @@ class GemmW8Args(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("A", C.c_void_p), ("Q", C.c_void_p), ("scale", C.c_void_p),
                 ("residual", C.c_void_p), ("C", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
                 ("lda", C.c_int64), ("ldq", C.c_int64), ("ldc", C.c_int64), ("ldr", C.c_int64), ("out_f32", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class GemmMxfp4Args(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("A", C.c_void_p), ("Q", C.c_void_p), ("scale", C.c_void_p),
+                ("residual", C.c_void_p), ("C", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
+                ("lda", C.c_int64), ("ldq", C.c_int64), ("lds", C.c_int64), ("ldc", C.c_int64), ("ldr", C.c_int64), ("out_f32", C.c_int32), ("reserved1", C.c_int32)]
 
 
 FX_NONE, FX_ROPE, FX_SWIGLU, FX_SWIGLU_BWD = 0, 1, 2, 3          # LLMSEG_FX_* of include/llmseg_hip.h
@@ -101,6 +107,8 @@ SIGNATURES = {
     "llmseg_gemm_set_variant": [C.c_int],
     "llmseg_quantize_rows_i8": [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p],
     "llmseg_gemm_w8": [C.POINTER(GemmW8Args), _p],
+    "llmseg_quantize_rows_mxfp4": [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p],
+    "llmseg_gemm_mxfp4": [C.POINTER(GemmMxfp4Args), _p],
     "llmseg_sample_tokens": [_p, _i64, _i64, _i64, _f32, _i32, _f32, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p],
     "llmseg_attn_fwd": [C.POINTER(AttnArgs), _p],
     "llmseg_attn_set_variant": [C.c_int],

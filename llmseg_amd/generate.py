@@ -57,9 +57,9 @@ class DecodeState:
         self.warm = False            # the state's first step ran eagerly (the step is captured at its second)
         self.fused = False           # decode step on merged-LoRA weights (+ norm / SwiGLU on the GEMM's A load for a single sequence)
         self.qkv_w = None            # per-layer q|k|v weights with the LoRA deltas merged in (fused steps)
-        self.bits = None             # weight_bits of the captured step (None = bf16 weights)
+        self.bits = None             # weight mode of the captured step: None = bf16 weights, 8 = weight_bits, "mxfp4" = weight_format
         self.ragged = False          # the captured step reads pos_rows (one position per sequence) instead of pos
-        self.w8 = None               # weight_bits = 8: {layer-matrix name: (q int8, scale fp32, w_hat bf16)} of `_quantize_w8`
+        self.w8 = None               # quantised modes: {layer-matrix name: (q int8, scale fp32, w_hat bf16)} of `_quantize_w8`, or (packed uint8, scale uint8, w_hat bf16) of `_quantize_mxfp4`
         self.beam_src = None         # beam search over the never-moved cache: int32 [N, capacity], key t of row r lives in physical row beam_src[r, t]
         self.src_a = self.src_b = None      # beam search: the table at a fixed address (the captured step reads it) and the buffer `ops.beam_step` re-orders it into
 
@@ -144,10 +144,12 @@ class GenerateMixin:
                 return F.norm(a, self._w(p + norm, F), None, c.eps, True)
             return ops.swiglu(a, c.inter) if swiglu else a
 
-        if st.bits is not None:                                # int8 rows; the A-load fusions of the bf16 route for a single sequence are not built for this kernel
+        if st.bits is not None:                                # int8 or MXFP4 rows; the A-load fusions of the bf16 route for a single sequence are not built for these kernels
+            rows = self._gemm_mxfp4_rows if st.bits == "mxfp4" else self._gemm_w8_rows
+
             def lin_w8(i, name, a, norm=None, swiglu=False, residual=None):
                 p = prefix(i)
-                return self._gemm_w8_rows(pre(p, a, norm, swiglu), *st.w8[p + name][:2], residual=residual)
+                return rows(pre(p, a, norm, swiglu), *st.w8[p + name][:2], residual=residual)
             return lin_w8
 
         members = {"qkv": [f"self_attn.{n}_proj.weight" for n in "qkv"], "gate_up": ["mlp.gate_proj.weight", "mlp.up_proj.weight"]}
@@ -227,9 +229,50 @@ class GenerateMixin:
         "qkv" (merged q|k|v), "self_attn.o_proj.weight", "gate_up" (gate|up) and "mlp.down_proj.weight"."""
         return {k: (b[0], b[1]) for k, b in self.__dict__["_w8"].items()}
 
+    def _quantize_mxfp4(self):
+        """weight_format = "mxfp4": the four matrices of every layer (W8_MATRICES, q|k|v with the LoRA deltas merged in) as MXFP4 rows -- packed E2M1 nibbles
+        and one E8M0 scale byte per 32 columns -- plus W^ = element * 2^e in bf16 (exact) for the prefill, from one `quantize_rows_mxfp4` launch per matrix into
+        persistent buffers (3.4 GB + 13 GB at Llama-7B).  Rebuilt from the CURRENT weights at every call, as the int8 mode does.  The cost (merge included) is
+        timed with a pair of events: `mxfp4_prepare_ms()`."""
+        c = self.config.llama
+        F = _Direct
+        ev = self.__dict__.get("_mxfp4_events")
+        if ev is None:
+            ev = self.__dict__["_mxfp4_events"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        merged = self._merge_lora() if c.lora_r > 0 else None
+        bufs = self.__dict__.setdefault("_mxfp4", {})
+        for i in range(c.layers):
+            p = f"model.layers.{i}."
+            src = (merged[i] if merged is not None else self._wcat(p + "qkv", [p + f"self_attn.{n}_proj.weight" for n in "qkv"], F),
+                   self._w(p + "self_attn.o_proj.weight", F),
+                   self._wcat(p + "gate_up", [p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], F),
+                   self._w(p + "mlp.down_proj.weight", F))
+            for name, w in zip(self.W8_MATRICES, src):
+                b = bufs.get(p + name)
+                if b is None:
+                    N, K = w.shape
+                    b = bufs[p + name] = (torch.empty((N, K // 2), device=w.device, dtype=torch.uint8), torch.empty((N, K // 32), device=w.device, dtype=torch.uint8),
+                                          torch.empty_like(w))
+                ops.quantize_rows_mxfp4(w, packed=b[0], scale=b[1], w_hat=b[2])
+        ev[1].record()
+        return bufs
+
+    def mxfp4_prepare_ms(self):
+        """Device time of the last `generate(weight_format="mxfp4")` call's LoRA merge + quantisation (waits for that work to finish)."""
+        ev = self.__dict__["_mxfp4_events"]
+        ev[1].synchronize()
+        return ev[0].elapsed_time(ev[1])
+
+    def decode_weights_mxfp4(self):
+        """{layer-matrix name: (packed uint8 [N, K / 2], scale uint8 [N, K / 32])} of the last `generate(weight_format="mxfp4")` call; the names are
+        `decode_weights_i8`'s."""
+        return {k: (b[0], b[1]) for k, b in self.__dict__["_mxfp4"].items()}
+
     def _prefill_w8(self, embeds, key_mask_u8, w8, kv_out):
-        """The prompt through the decoder stack of the QUANTISED model: the no-grad kernel sequence of `_llama` on W^ = bf16(q * scale), so that
-        prefill and decode steps run one model (the one a cache-free forward on the dequantised state dict runs).  -> final-norm hidden [N, T, H]."""
+        """The prompt through the decoder stack of the QUANTISED model: the no-grad kernel sequence of `_llama` on W^ (entry [2] of every matrix: bf16(q * scale)
+        of the int8 mode, the exact element * 2^e of MXFP4), so that prefill and decode steps run one model (the one a cache-free forward on the dequantised
+        state dict runs).  -> final-norm hidden [N, T, H]."""
         c = self.config.llama
         F = _Direct
         N, T, H = embeds.shape
@@ -259,6 +302,17 @@ class GenerateMixin:
             ops.gemm_w8(a[r:r + 8], q, scale, residual=None if residual is None else residual[r:r + 8], out=out[r:r + 8])
         return out
 
+    @staticmethod
+    def _gemm_mxfp4_rows(a, packed, scale, residual=None):
+        """`ops.gemm_mxfp4` (at most 8 rows a call) on any number of rows, in chunks of 8 as `_gemm_w8_rows`."""
+        M = a.shape[0]
+        if M <= 8:
+            return ops.gemm_mxfp4(a, packed, scale, residual=residual)
+        out = torch.empty((M, packed.shape[0]), device=a.device, dtype=BF16)
+        for r in range(0, M, 8):
+            ops.gemm_mxfp4(a[r:r + 8], packed, scale, residual=None if residual is None else residual[r:r + 8], out=out[r:r + 8])
+        return out
+
     def _decode_step(self, st, use_graph=True):
         """Run one decode step; from the second step of a state on, replay it from a hipGraph (captured once per (N, capacity): a step is
         ~420 launches of 5-20 us kernels, the host cannot issue them as fast as the GPU finishes them)."""
@@ -275,7 +329,7 @@ class GenerateMixin:
         st.graph.replay()
 
     def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, weight_bits, fused, key):
-        """What every generate() route does before its loop: the prompts (input_ids [N, L], trimmed; attention_mask = the ragged call's mask, else None) through
+        """(weight_bits: the call's weight mode -- None, 8, or "mxfp4" for weight_format.)  What every generate() route does before its loop: the prompts (input_ids [N, L], trimmed; attention_mask = the ragged call's mask, else None) through
         the prefill, K and V of prompt n into physical row n * rows of the decode state of N * rows rows (rows = 1, or the beams per prompt), the state made ready
         for the call's route.  The states are kept per (N * rows, capacity) + key.  -> (state, final-norm hidden [N, T, H], T, embedding weights, lm_head weights)."""
         self.prepare()
@@ -307,7 +361,7 @@ class GenerateMixin:
             st.w8 = None
             hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
         else:
-            st.w8 = self._quantize_w8()
+            st.w8 = self._quantize_mxfp4() if weight_bits == "mxfp4" else self._quantize_w8()
             hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
         ragged = attention_mask is not None or rows > 1       # beams: every row at its own device-side position (they are equal; the per-row kernels read them)
         if fused != st.fused or weight_bits != st.bits or ragged != st.ragged:
@@ -318,7 +372,8 @@ class GenerateMixin:
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
                  weight_bits=None, attention_mask=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None,
-                 return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False, return_beam_scores=False, beam_cache="indirect", _beam_trace=None):
+                 return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False, return_beam_scores=False, beam_cache="indirect", _beam_trace=None,
+                 weight_format=None):
         """Greedy generation (or sampling: do_sample, or beam search: num_beams, both below).  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
         IMAGE_TOKEN_INDEX each.
         -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
@@ -336,6 +391,14 @@ class GenerateMixin:
         `decode_weights_i8()` returns them.  Measured at Llama-7B (profiles/w8_decode.md): 2.70 / 2.85 / 3.40 / 4.97 ms per token at 1 / 2 / 4 / 8 sequences
         against 3.33 / 3.88 / 4.33 / 5.08 in bf16 -- at 8 sequences there is no gain (the int8 kernel takes as long as the bf16 kernel there, whatever
         the FMA form) -- and 9.4 ms per call for the merge + quantisation, repaid after about 11 tokens at one sequence.
+        weight_format = "mxfp4" (opt-in; needs fuse_decode, the LoRA is merged first; not together with weight_bits): the same scheme on OCP MXFP4 rows -- 4-bit
+        E2M1 elements with one power-of-two E8M0 scale per 32 columns, 4.25 bits per weight (`ops.quantize_rows_mxfp4`; the rule is stated in include/llmseg_hip.h).
+        W^ = element * 2^e is exact in bf16, so the prefill (on W^) and the decode steps (`ops.gemm_mxfp4` on the packed rows: the vector ALU at 1-2 rows, the
+        matrix cores from 3) run exactly one model; lm_head, embeddings, norms, the KV cache and attention stay bf16.  Re-quantised at every call
+        (`mxfp4_prepare_ms()`); `decode_weights_mxfp4()` returns the packed rows and scale bytes.  It composes with attention_mask, do_sample, num_beams and
+        use_graph as weight_bits=8 does.  Measured at Llama-7B (profiles/mxfp4_decode.md): 2.09 / 2.71 / 3.01 / 3.41 ms per token at 1 / 2 / 4 / 8 sequences against
+        int8's 2.71 / 2.89 / 3.42 / 4.99 and bf16's 3.35 / 3.88 / 4.32 / 5.08 in one session (disjoint ranges everywhere; the smallest gain over int8, 7 %, is at 2
+        sequences) and 9.1 ms per call for the merge + quantisation.  At one sequence 1.1 of the 2.09 ms are the step's non-GEMM launches.
         do_sample=True: every token is drawn by `ops.sample_tokens` (ONE launch per step: temperature, top-k, top-p, the draw and the eos / pad
         bookkeeping; the rule is stated in include/llmseg_hip.h) instead of the arg-max; everything before the pick -- prefill, decode step,
         hipGraph, weight_bits, attention_mask -- is the greedy route's.  temperature > 0; top_k >= 0 with 0 = OFF (Hugging Face's default is 50:
@@ -355,7 +418,7 @@ class GenerateMixin:
         loop re-orders K and V physically (`index_select` over every layer) and runs the `llmseg_decode_attn_rows` step -- the same bits, kept as the
         yardstick (profiles/beam_search.md).  Results: sequences [N, L + n_new] with n_new the longest winning length, row i = its prompt, its tokens (eos
         included), then pad_token_id; hidden [N, T + n_new - 1, H] = row i's T prefill states, the state of each fed token of the winner, then zeros;
-        return_beam_scores=True adds fp32 [N], the winner's value.  weight_bits=8 and use_graph work as in the greedy route.  Out of scope (ValueError):
+        return_beam_scores=True adds fp32 [N], the winner's value.  weight_bits=8, weight_format="mxfp4" and use_graph work as in the greedy route.  Out of scope (ValueError):
         do_sample together with beams (beam sampling); an attention_mask that is ragged after trimming; fuse_decode=False; head_dim != 128; num_beams > 16 or
         2 * num_beams > vocab; early_stopping="never"; several returned sequences, diverse groups and constraints have no argument.  With num_beams == 1
         the other beam arguments must stay at their defaults, and not one launch of the routes above changes."""
@@ -398,12 +461,20 @@ class GenerateMixin:
             raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
         if weight_bits == 8 and not fuse_decode:
             raise ValueError("weight_bits=8 needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
+        if weight_format not in (None, "mxfp4"):
+            raise ValueError(f"weight_format must be None or 'mxfp4' (E2M1 elements with one E8M0 scale per 32), got {weight_format!r}")
+        if weight_format is not None:
+            if weight_bits is not None:
+                raise ValueError("weight_format='mxfp4' and weight_bits=8 are two quantised modes: pass one of them")
+            if not fuse_decode:
+                raise ValueError("weight_format='mxfp4' needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
+        mode = weight_bits if weight_format is None else weight_format      # None | 8 | "mxfp4": what the prefill and the decode state are keyed by
         if num_beams >= 2:
             if not defaults:
                 raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True")
             if weight_bits not in (None, 8):
                 raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
-            return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, weight_bits, attention_mask, num_beams,
+            return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, mode, attention_mask, num_beams,
                                         float(length_penalty), early_stopping, return_beam_scores, beam_cache, _beam_trace)
         lens = None                                            # prompt lengths L_i on the host, ragged calls only
         if attention_mask is not None:
@@ -417,7 +488,7 @@ class GenerateMixin:
             fill = 0 if pad_token_id is None else int(pad_token_id)
             input_ids = torch.where(attention_mask.to(input_ids.device), input_ids, torch.full_like(input_ids, fill))
         ragged = lens is not None
-        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, weight_bits, bool(fuse_decode), ())
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, mode, bool(fuse_decode), ())
         dev = self.device_
         N, L = input_ids.shape
         Pn, H = self.config.n_img_tokens, self.config.llama.hidden

@@ -207,6 +207,53 @@ def gemm_w8(a, q, scale, residual=None, out=None, out_f32=False):
     return out
 
 
+def quantize_rows_mxfp4(w, want_hat=False, packed=None, scale=None, w_hat=None):
+    """MXFP4 quantisation of w [N, K] bf16 (K % 32 == 0, rows 16-byte aligned): -> (packed uint8 [N, K / 2], scale uint8 [N, K / 32]) and, with want_hat,
+    w_hat bf16 [N, K] = element * 2^e (exact) from the same pass.  Per block of 32 columns: e = the smallest integer with amax <= 6 * 2^e, scale byte e + 127
+    (E8M0); elements are E2M1 codes, rounded to nearest with ties to the even code, element 2 j in the low nibble of byte j; the arithmetic is stated in
+    include/llmseg_hip.h.  packed / scale / w_hat: existing buffers to write into (w_hat implies want_hat; a packed row pitch must be a multiple of 16 bytes)."""
+    _req(w)
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    assert K % 32 == 0, K
+    if packed is None:
+        packed = torch.empty((N, K // 2), device=w.device, dtype=torch.uint8)       # K % 32 == 0: the pitch is a multiple of 16 bytes
+    if scale is None:
+        scale = torch.empty((N, K // 32), device=w.device, dtype=torch.uint8)
+    if w_hat is None and want_hat:
+        w_hat = torch.empty((N, K), device=w.device, dtype=BF16)
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.shape == (N, K // 2) and packed.stride(1) == 1
+    assert scale.is_cuda and scale.dtype == torch.uint8 and scale.shape == (N, K // 32) and scale.stride(1) == 1
+    assert w_hat is None or (_req(w_hat).shape == (N, K) and w_hat.stride(1) == 1)
+    _lib.check(_lib.load().llmseg_quantize_rows_mxfp4(_ptr(w), w.stride(0), N, K, _ptr(packed), packed.stride(0), _ptr(scale), scale.stride(0), _ptr(w_hat),
+                                                      0 if w_hat is None else w_hat.stride(0), _stream()), "quantize_rows_mxfp4")
+    return (packed, scale, w_hat) if w_hat is not None else (packed, scale)
+
+
+def gemm_mxfp4(a, packed, scale, residual=None, out=None, out_f32=False):
+    """out[M, N] = residual + a [M, K] bf16 @ w_hat [N, K] ^T, M <= 8, with w_hat decoded on the fly from MXFP4 rows (`quantize_rows_mxfp4`: packed uint8
+    [N, K / 2], scale uint8 [N, K / 32]): the decode step's weight stream at 4.25 bits per weight.  The products are exact in fp32 and accumulated in fp32;
+    out bf16, or fp32 with out_f32."""
+    _req(a)
+    assert a.dim() == 2 and packed.dim() == 2 and scale.dim() == 2 and a.stride(1) == 1 and packed.stride(1) == 1 and scale.stride(1) == 1
+    assert packed.is_cuda and packed.dtype == torch.uint8 and scale.is_cuda and scale.dtype == torch.uint8
+    M, K = a.shape
+    N = packed.shape[0]
+    assert K % 32 == 0 and packed.shape[1] == K // 2 and scale.shape == (N, K // 32) and M <= 8, (a.shape, packed.shape, scale.shape)
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else BF16)
+    else:
+        out_f32 = out.dtype == torch.float32
+    assert out.shape == (M, N) and out.stride(1) == 1 and (out_f32 or out.dtype == BF16)
+    if residual is not None:
+        assert _req(residual).shape == (M, N) and residual.stride(1) == 1
+    g = _lib.GemmMxfp4Args(A=a.data_ptr(), Q=packed.data_ptr(), scale=scale.data_ptr(), residual=None if residual is None else residual.data_ptr(), C=out.data_ptr(),
+                           M=M, N=N, K=K, lda=a.stride(0), ldq=packed.stride(0), lds=scale.stride(0), ldc=out.stride(0),
+                           ldr=0 if residual is None else residual.stride(0), out_f32=1 if out_f32 else 0)
+    _lib.check(_lib.load().llmseg_gemm_mxfp4(C.byref(g), _stream()), "gemm_mxfp4")
+    return out
+
+
 def sample_tokens(logits, temperature, top_k, top_p, u, eos_token_id=None, pad_token_id=0, unfinished=None, want_logprob=False, want_kept=False,
                   want_probs=False, next=None, logprob=None, kept=None, probs=None):
     """One token per row of logits [N, V] bf16 (rows may be strided) by the rule of include/llmseg_hip.h (`llmseg_sample_tokens`): temperature > 0,
