@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args, 5 = llmseg_lora_down_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (19: llmseg_quantize_rows_mxfp4, llmseg_gemm_mxfp4 and llmseg_gemm_mxfp4_args; 18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (20: llmseg_logits_process; 19: llmseg_quantize_rows_mxfp4, llmseg_gemm_mxfp4 and llmseg_gemm_mxfp4_args; 18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 19
+#define LLMSEG_ABI_VERSION 20
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -231,6 +231,36 @@ int llmseg_gemm_mxfp4(const llmseg_gemm_mxfp4_args* args, void* stream);
 int llmseg_sample_tokens(const void* logits, int64_t ldl, int64_t N, int64_t V, float temperature, int32_t top_k, float top_p, const float* u,
                          int64_t eos, int64_t pad, int64_t* unfinished /* nullable, in/out */, int64_t* next, float* logprob /* nullable */,
                          int32_t* kept /* nullable */, float* probs /* nullable */, int64_t ldp, void* stream);
+
+/* ---- logits processors (generate(repetition_penalty=, no_repeat_ngram_size=, min_new_tokens=, suppress_tokens=)): ONE launch per token ----
+ * Per row n: the logits l (bf16, V entries of logits[n][.], rewritten IN PLACE) and the row's history h[0 .. len): its prompt ids as given (the <image> placeholder
+ * -200 stays in as it is) followed by every token it has emitted so far.  First the append, when `append` is given: append[n] is written at hist[n][hist_len[n]]
+ * and hist_len[n] grows by 1; a full row (hist_len[n] >= ld_hist) drops the write and does not count it.  hist_len[n] is clamped to [0, ld_hist] when read.  Then,
+ * on the history INCLUDING the appended token, in Hugging Face's order (processors come before the warpers of llmseg_sample_tokens):
+ *   1. repetition penalty theta > 0 (1 = off): every DISTINCT token t of the history with 0 <= t < V, exactly once however often it occurs:
+ *      l_t <- bf16(fl32(l_t) * fl32(theta)) if l_t < 0, else bf16(fl32(l_t) / fl32(theta)): a true fp32 division, the result rounded to nearest even; -0.0 (not
+ *      < 0: divided, stays -0.0), +inf, -inf and NaN (the canonical quiet NaN 0x7fc0) fall out of that formula.  This is RepetitionPenaltyLogitsProcessor on a
+ *      bf16 tensor, bit for bit.
+ *   2. no-repeat n-gram g >= 0 (0 = off): if len >= g, for every j in [0, len - g] with h[j .. j + g - 2] == h[len - g + 1 .. len - 1] (raw int64 values), the
+ *      token h[j + g - 1] gets -inf if it lies in [0, V).  g = 1 bans every token of the history; len < g bans nothing.  (NoRepeatNGramLogitsProcessor; the prompt
+ *      counts, as it does there.)
+ *   3. minimum length: l_ban <- -inf for ban_token >= 0 (-1 = none).  All rows step together, so the host knows how many tokens were emitted and passes the eos id
+ *      while fewer than min_new_tokens were (MinNewTokensLengthLogitsProcessor).
+ *   4. suppressed tokens: every id of the device list suppress[0 .. n_suppress) that lies in [0, V) gets -inf (SuppressTokensLogitsProcessor; the Python wrapper
+ *      refuses ids outside [0, V) given on the host).
+ * Steps 2 to 4 only write -inf, and a penalised -inf stays -inf (theta > 0), so the result does not depend on the order of the steps.  A row that ends up with every
+ * logit -inf gives an unspecified token of [0, V) at the pick.  Two deviations from Hugging Face: history values outside [0, V) are skipped by steps 1 and 2 (HF's
+ * gather on -200 is an out-of-range index; inside a compared window they still compare as values); and the history of a finished row goes on collecting `pad`, which is
+ * harmless because a finished row emits `pad` whatever its logits say.
+ * One workgroup per row; only the O(len) affected logits are touched, never the whole row.  A token at several history positions is penalised ONCE: every thread
+ * loads the original logit of ALL its positions, a barrier, then every thread stores f(original) -- duplicates store the same bits -- which holds because the whole
+ * history is loaded before the first store: hence the cap on ld_hist.  The -inf writes follow a second barrier.  No floating-point atomics: a pure function of the inputs.
+ * Checked before the launch (LLMSEG_EINVAL): logits, hist, hist_len non-NULL; alignment (8 for int64, 4 for int32, 2 for bf16); N >= 1; 1 <= V < 2^31; ldl >= V;
+ * 1 <= ld_hist <= LLMSEG_LOGITS_HIST_CAP; theta finite and > 0; no_repeat_ngram >= 0; ban_token in [-1, V); n_suppress >= 0, and 0 exactly when suppress is NULL. */
+#define LLMSEG_LOGITS_HIST_CAP 4096
+int llmseg_logits_process(void* logits, int64_t ldl, int64_t N, int64_t V, int64_t* hist, int64_t ld_hist, int32_t* hist_len /* in/out */,
+                          const int64_t* append /* nullable */, float repetition_penalty, int32_t no_repeat_ngram, int64_t ban_token,
+                          const int32_t* suppress /* nullable */, int64_t n_suppress, void* stream);
 
 /* ---- beam search (generate(num_beams >= 2)): one pick per token, TWO launches ----
  * N prompts, B = num_beams live beams each (2 <= B <= 16), V >= 2 B.  Inputs: logits bf16 [N * beams_in][ldl] (beams_in = 1 for the first pick, which reads the

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 19         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 20         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
 NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
@@ -110,6 +110,7 @@ SIGNATURES = {
     "llmseg_quantize_rows_mxfp4": [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p],
     "llmseg_gemm_mxfp4": [C.POINTER(GemmMxfp4Args), _p],
     "llmseg_sample_tokens": [_p, _i64, _i64, _i64, _f32, _i32, _f32, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p],
+    "llmseg_logits_process": [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _f32, _i32, _i64, _p, _i64, _p],
     "llmseg_attn_fwd": [C.POINTER(AttnArgs), _p],
     "llmseg_attn_set_variant": [C.c_int],
     "llmseg_attn_bwd": [C.POINTER(AttnBwdArgs), _p],

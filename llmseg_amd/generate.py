@@ -373,7 +373,7 @@ class GenerateMixin:
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
                  weight_bits=None, attention_mask=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None,
                  return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False, return_beam_scores=False, beam_cache="indirect", _beam_trace=None,
-                 weight_format=None):
+                 weight_format=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None):
         """Greedy generation (or sampling: do_sample, or beam search: num_beams, both below).  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
         IMAGE_TOKEN_INDEX each.
         -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
@@ -421,7 +421,41 @@ class GenerateMixin:
         return_beam_scores=True adds fp32 [N], the winner's value.  weight_bits=8, weight_format="mxfp4" and use_graph work as in the greedy route.  Out of scope (ValueError):
         do_sample together with beams (beam sampling); an attention_mask that is ragged after trimming; fuse_decode=False; head_dim != 128; num_beams > 16 or
         2 * num_beams > vocab; early_stopping="never"; several returned sequences, diverse groups and constraints have no argument.  With num_beams == 1
-        the other beam arguments must stay at their defaults, and not one launch of the routes above changes."""
+        the other beam arguments must stay at their defaults, and not one launch of the routes above changes.
+        repetition_penalty (> 0, 1 = off), no_repeat_ngram_size (>= 0, 0 = off), min_new_tokens (>= 0; needs eos_token_id) and suppress_tokens (a sequence of ids in
+        [0, vocab)): Hugging Face's RepetitionPenalty / NoRepeatNGram / MinNewTokensLength / SuppressTokens logits processors, in that order, as ONE launch per token
+        (`ops.logits_process`, `llmseg_logits_process`; the rule is stated in include/llmseg_hip.h and equals the HF processors on bf16 logits bit for bit) that rewrites
+        the step's logits in place BEFORE the pick: the arg-max, or `ops.sample_tokens` (processors come before the warpers, HF's order; return_logprobs then refers to
+        the processed distribution).  With any of the four off its default the call keeps each row's history -- its own prompt ids (the <image> placeholder stays in
+        and is skipped: HF would index out of range), then every token it emitted -- in one device buffer int64 [N, Lm + max_new_tokens] that the same launch appends
+        to, so Lm + max_new_tokens must not exceed `ops.LOGITS_HIST_CAP` (4096).  The history of a finished row goes on collecting pad_token_id (harmless: such a row
+        emits pad whatever its logits say).  The decode step is untouched (the pick is outside the captured graph), so use_graph, fuse_decode, weight_bits,
+        weight_format, attention_mask and do_sample all compose.  With all four at their defaults no history is built, `ops.logits_process` is never called and every
+        route is launch for launch the one above.  Measured at Llama-7B (profiles/generation_controls.md): the four controls add 0.007 / -0.001 ms per token at 1 / 8
+        sequences (inside the run-to-run spread) where Hugging Face's processor objects on the device add 0.104 / 0.122.  Out of scope (ValueError): any of the four with
+        num_beams >= 2 -- HF applies processors to the log-softmax there, not to the logits: another rule and another `beam_step`."""
+        controls = not (repetition_penalty == 1.0 and no_repeat_ngram_size == 0 and min_new_tokens == 0 and suppress_tokens is None)
+        if controls:                                           # any of the four off its default: the logits-processor launch before every pick
+            if isinstance(repetition_penalty, bool) or not (isinstance(repetition_penalty, (int, float)) and math.isfinite(repetition_penalty) and repetition_penalty > 0):
+                raise ValueError(f"repetition_penalty must be a finite number > 0 (1 = off), got {repetition_penalty!r}")
+            for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+                if not (isinstance(v, int) and not isinstance(v, bool) and 0 <= v < 2 ** 31):
+                    raise ValueError(f"{name} must be an integer >= 0 (0 = off), got {v!r}")
+            if min_new_tokens > 0 and eos_token_id is None:
+                raise ValueError("min_new_tokens needs an eos_token_id: it bans that token until enough tokens were emitted")
+            if min_new_tokens > max_new_tokens:
+                raise ValueError(f"min_new_tokens = {min_new_tokens} exceeds max_new_tokens = {max_new_tokens}")
+            if suppress_tokens is not None:
+                vocab = self.config.llama.vocab
+                try:
+                    suppress_tokens = list(suppress_tokens)
+                except TypeError:
+                    raise ValueError(f"suppress_tokens must be a sequence of integers in [0, {vocab}), got {suppress_tokens!r}") from None
+                if not suppress_tokens or not all(isinstance(t, int) and not isinstance(t, bool) and 0 <= t < vocab for t in suppress_tokens):
+                    raise ValueError(f"suppress_tokens must be a non-empty sequence of integers in [0, vocab = {vocab}), got {suppress_tokens!r}")
+            if isinstance(num_beams, int) and num_beams >= 2:
+                raise ValueError("repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens with num_beams >= 2 are out of scope: beam search applies "
+                                 "processors to the log-softmax, another rule")
         if not (isinstance(num_beams, int) and not isinstance(num_beams, bool) and num_beams >= 1):
             raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
         if beam_cache not in ("indirect", "copy"):
@@ -488,6 +522,9 @@ class GenerateMixin:
             fill = 0 if pad_token_id is None else int(pad_token_id)
             input_ids = torch.where(attention_mask.to(input_ids.device), input_ids, torch.full_like(input_ids, fill))
         ragged = lens is not None
+        if controls and input_ids.shape[1] + max_new_tokens > ops.LOGITS_HIST_CAP:
+            raise ValueError(f"repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens keep a history of prompt + max_new_tokens = "
+                             f"{input_ids.shape[1]} + {max_new_tokens} ids per row: more than the cap of {ops.LOGITS_HIST_CAP}")
         st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, mode, bool(fuse_decode), ())
         dev = self.device_
         N, L = input_ids.shape
@@ -515,7 +552,16 @@ class GenerateMixin:
                 uniforms = torch.rand((N, max_new_tokens), device=dev, dtype=torch.float32, generator=gen)
             u_steps = uniforms.to(dev).t().contiguous()        # [max_new_tokens, N]: step s reads one contiguous row
             lps = []
+        if controls:                                           # each row's history at a fixed address: its own prompt, left-aligned; the launch below appends to it
+            hist = torch.zeros((N, L + max_new_tokens), dtype=torch.int64, device=dev)
+            hist[:, :L] = seqs[0]
+            hist_len = (lens.to(torch.int32) if ragged else torch.full((N,), L, dtype=torch.int32)).to(dev)
+            suppress = None if suppress_tokens is None else torch.tensor(suppress_tokens, dtype=torch.int32, device=dev)
+            nxt = None
         while True:
+            if controls:                                       # one launch: the token just picked joins the history, then the processors rewrite the step's logits in place
+                logits = ops.logits_process(logits, hist, hist_len, append=nxt, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                            ban_token=eos_token_id if n_new < min_new_tokens else None, suppress=suppress)
             if do_sample:                                      # one launch: the pick, pad for finished rows and the update of `unfinished`
                 nxt, lp, _, _ = ops.sample_tokens(logits, temperature, top_k, top_p, u_steps[n_new], eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                                   unfinished=unfinished, want_logprob=return_logprobs)

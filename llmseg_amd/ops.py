@@ -286,6 +286,32 @@ def sample_tokens(logits, temperature, top_k, top_p, u, eos_token_id=None, pad_t
     return next, logprob, kept, probs
 
 
+LOGITS_HIST_CAP = 4096              # == LLMSEG_LOGITS_HIST_CAP of include/llmseg_hip.h
+
+
+def logits_process(logits, hist, hist_len, append=None, repetition_penalty=1.0, no_repeat_ngram_size=0, ban_token=None, suppress=None):
+    """The logits processors of include/llmseg_hip.h (`llmseg_logits_process`) on logits [N, V] bf16 (rows may be strided), IN PLACE, one launch: `append` (int64 [N],
+    None = nothing) is stored at hist[n, hist_len[n]] and counted (dropped when the row is full), then the repetition penalty (1 = off), the n-gram ban (0 = off),
+    `ban_token` (None = none) and the `suppress` list (int32 device tensor or a sequence of ints in [0, V); None = none) act on the row's history hist[n, :hist_len[n]].
+    hist int64 [N, cap <= LOGITS_HIST_CAP] (dense rows) and hist_len int32 [N] are updated in place.  -> logits."""
+    _req(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    N, V = logits.shape
+    # dense rows: the entry point's ld_hist is both the row stride and the row's capacity
+    assert hist.is_cuda and hist.dtype == torch.int64 and hist.dim() == 2 and hist.shape[0] == N and hist.stride(1) == 1 and (N == 1 or hist.stride(0) == hist.shape[1])
+    assert hist_len.is_cuda and hist_len.dtype == torch.int32 and hist_len.shape == (N,) and hist_len.is_contiguous()
+    assert append is None or (append.is_cuda and append.dtype == torch.int64 and append.shape == (N,) and append.is_contiguous())
+    if suppress is not None and not torch.is_tensor(suppress):
+        ids = [int(t) for t in suppress]
+        assert ids and all(0 <= t < V for t in ids), f"suppress must be a non-empty list of ids in [0, {V})"
+        suppress = torch.tensor(ids, dtype=torch.int32, device=logits.device)
+    assert suppress is None or (suppress.is_cuda and suppress.dtype == torch.int32 and suppress.dim() == 1 and suppress.numel() > 0 and suppress.is_contiguous())
+    _lib.check(_lib.load().llmseg_logits_process(_ptr(logits), max(logits.stride(0), V) if N == 1 else logits.stride(0), N, V, _ptr(hist), hist.shape[1], _ptr(hist_len),
+                                                 _ptr(append), float(repetition_penalty), int(no_repeat_ngram_size), -1 if ban_token is None else int(ban_token),
+                                                 _ptr(suppress), 0 if suppress is None else suppress.numel(), _stream()), "logits_process")
+    return logits
+
+
 def gemm_batched(a, w, out, M, N, K, lda, ldw, ldc, batch, sA, sW, sC, out_f32=True, alpha=1.0, trans_a=False, trans_w=False,
                  batch2=1, sA2=0, sW2=0, sC2=0):
     """Strided-batched GEMM on raw strides (elements); used for the per-head q.R^T relative-position products."""
