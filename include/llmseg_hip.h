@@ -463,7 +463,9 @@ int llmseg_nms(const float* boxes, const int32_t* order, int32_t n, float iou_th
  *   llmseg_image_resize_u8: `ResizeLongestSide.apply_image` (model/segment_anything/utils/transforms.py:27-35, called by
  *     `SamPredictor.set_image`, predictor.py:34-60) = Pillow's 8-bit BILINEAR `Image.resize`, bit-identical.  in uint8 [in_h][in_w][channels]
  *     with `in_row_stride` bytes between rows -- a crop of a crop layer (automatic_mask_generator.py:254-257) is an origin pointer + the full
- *     image's row stride; out uint8 [out_h][out_w][channels] dense.  workspace >= llmseg_image_resize_workspace(...) bytes.
+ *     image's row stride; out uint8 [out_h][out_w][channels] dense.  workspace >= llmseg_image_resize_workspace(...) bytes (its layout is
+ *     stated once, below llmseg_mask_union).  "Bit-identical to Pillow" holds per channel, 1 <= channels <= 4: Pillow premultiplies `LA` /
+ *     `RGBA` images by their alpha before it resamples them, this kernel resamples every channel on its own and should.
  *   llmseg_sam_preprocess: `Sam.preprocess` (modeling/sam.py:174-186): in uint8 [h][w][3] -> out bf16 [3][img_size][img_size],
  *     (x - mean[c]) / std[c] inside the image, zero in the padding; mean / std are HOST pointers to 3 floats.
  *   llmseg_mask_small_regions: `remove_small_regions(mask, min_area, "holes")` then `(..., "islands")` (utils/amg.py:267-291, as
@@ -496,7 +498,18 @@ int llmseg_mask_boxes(const uint8_t* masks, int32_t K, int32_t H, int32_t W, int
  *     workspace >= llmseg_clip_preprocess_workspace(h, w, size) bytes.
  *   llmseg_mask_union: out uint8 [C][H][W] = 1 where any mask k with select[c][k] != 0 is non-zero, else 0 (the union of the chosen proposals,
  *     training.py:712-733).  masks uint8 [K][H][W], select uint8 [C][K] on the DEVICE (no host synchronisation); masks that no row selects
- *     are not read.  16-byte accesses where the addresses are 16-byte aligned. */
+ *     are not read.  16-byte accesses where the addresses are 16-byte aligned.
+ * Workspace of llmseg_image_resize_workspace / llmseg_image_resize_filter_workspace / llmseg_clip_preprocess_workspace, as the calls leave it
+ * (tests read the tap tables back and compare them with Pillow's `precompute_coeffs` + `normalize_coeffs_8bpc` integer for integer):
+ *   horizontal table   at byte 0: out_w rows (`size` rows for CLIP) of ksize + 2 int32, a row = {first input index, tap count, taps zero-filled
+ *                      to ksize}, ksize = 2 * ceil(support) + 1 with support = max(in / out, 1) (BILINEAR) or twice that (BICUBIC).  Written
+ *                      only when the width changes.
+ *   vertical table     at the next 256-byte boundary: out_h rows (`size` for CLIP) in the same form, written only when the height changes.
+ *   intermediate       at the next 256-byte boundary: uint8 [in_h][out_w][channels], written only when both passes run (CLIP: the rows
+ *                      the window's vertical taps reach x `size` columns, whenever the width changes).
+ *   CLIP tables hold the crop window's output indices only (columns left .. left + size, rows top .. top + size of the resized image); the
+ *   vertical one stores its first indices minus the first input row the call reads.
+ *   A call depends on nothing the workspace held before, and ksize <= 64 (BILINEAR) / 256 (BICUBIC) on both axes or the call is refused. */
 enum { LLMSEG_RESAMPLE_BILINEAR = 0, LLMSEG_RESAMPLE_BICUBIC = 1 };
 int64_t llmseg_image_resize_filter_workspace(int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, int32_t channels, int32_t filter);
 int llmseg_image_resize_u8_filter(const uint8_t* in, int64_t in_row_stride, uint8_t* out, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,

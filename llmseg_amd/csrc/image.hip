@@ -22,7 +22,12 @@
 // Pillow's resampling (src/libImaging/Resample.c): per output index the taps are triangle weights around center = (xx + 0.5) * scale over
 // [center - support, center + support), support = max(scale, 1), normalised in double and rounded to 22-bit fixed point; a pass is
 // out = clip8((2^21 + sum in * k) >> 22); horizontal pass first (uint8 intermediate), then vertical.  The tap table is computed on the device
-// in double with the SAME operation order and no fused multiply-adds (a contraction changes the rounding of w * 2^22 + 0.5).
+// in double with the SAME operation order and no fused multiply-adds.  A contraction of (xx + 0.5) * scale -/+ support puts the centre into
+// the first / last index unrounded; where Pillow's rounded sum is an integer the truncation then gives its neighbour (bilinear 2 -> 6,
+// output index 4: {first 0, count 2} for Pillow's {first 1, count 1}; the extra tap has weight 0).  The table kernels therefore use PLAIN
+// operators under `#pragma clang fp contract(off)`.  The pragma is lexical: it does not reach the bodies of header functions such as
+// __dmul_rn / __dadd_rn (`return x * y;` compiled under the default -ffp-contract=fast), whose results the backend fuses after inlining.
+// tests/test_image_kernels_gpu.py reads the tables back out of the workspace and compares them integer for integer.
 #include "common.h"
 #include "llmseg_hip.h"
 
@@ -36,33 +41,33 @@ __global__ __launch_bounds__(256) void pil_taps_kernel(int32_t* __restrict__ tab
 #pragma clang fp contract(off)
   const int xx = blockIdx.x * blockDim.x + threadIdx.x;
   if (xx >= out_size) return;
-  const double scale = __ddiv_rn((double)in_size, (double)out_size);
+  const double scale = (double)in_size / (double)out_size;
   const double filterscale = scale < 1.0 ? 1.0 : scale;
   const double support = filterscale;                       // bilinear: 1.0 * filterscale
-  const double ss = __ddiv_rn(1.0, filterscale);
-  const double center = __dmul_rn(__dadd_rn((double)xx, 0.5), scale);
-  int lo = (int)__dadd_rn(__dsub_rn(center, support), 0.5);
+  const double ss = 1.0 / filterscale;
+  const double center = ((double)xx + 0.5) * scale;
+  int lo = (int)(center - support + 0.5);
   if (lo < 0) lo = 0;
-  int hi = (int)__dadd_rn(__dadd_rn(center, support), 0.5);
+  int hi = (int)(center + support + 0.5);
   if (hi > in_size) hi = in_size;
   const int n = hi - lo;
   double w[MAX_TAPS];
   double ww = 0.0;
   for (int x = 0; x < n; ++x) {
-    double a = __dmul_rn(__dadd_rn(__dsub_rn((double)(x + lo), center), 0.5), ss);
+    double a = ((double)(x + lo) - center + 0.5) * ss;
     if (a < 0.0) a = -a;
-    const double v = a < 1.0 ? __dsub_rn(1.0, a) : 0.0;
+    const double v = a < 1.0 ? 1.0 - a : 0.0;
     w[x] = v;
-    ww = __dadd_rn(ww, v);
+    ww = ww + v;
   }
   int32_t* row = tab + (long)xx * (ksize + 2);
   row[0] = lo; row[1] = n;
   for (int x = 0; x < ksize; ++x) {
     int k = 0;
     if (x < n) {
-      const double v = ww != 0.0 ? __ddiv_rn(w[x], ww) : w[x];
-      const double f = __dmul_rn(v, (double)(1 << PIL_BITS));
-      k = v < 0.0 ? (int)__dadd_rn(-0.5, f) : (int)__dadd_rn(0.5, f);
+      const double v = ww != 0.0 ? w[x] / ww : w[x];
+      const double f = v * (double)(1 << PIL_BITS);
+      k = v < 0.0 ? (int)(-0.5 + f) : (int)(0.5 + f);
     }
     row[2 + x] = k;
   }
@@ -97,8 +102,8 @@ constexpr int MAX_TAPS_CUBIC = 256;
 __device__ __forceinline__ double pil_bicubic(double x) {
 #pragma clang fp contract(off)
   if (x < 0.0) x = -x;
-  if (x < 1.0) return __dadd_rn(__dmul_rn(__dmul_rn(__dsub_rn(__dmul_rn(1.5, x), 2.5), x), x), 1.0);
-  if (x < 2.0) return __dmul_rn(__dsub_rn(__dmul_rn(__dadd_rn(__dmul_rn(__dsub_rn(x, 5.0), x), 8.0), x), 4.0), -0.5);
+  if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;
+  if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5;
   return 0.0;
 }
 
@@ -110,28 +115,28 @@ __global__ __launch_bounds__(256) void pil_taps_cubic_kernel(int32_t* __restrict
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= count) return;
   const int xx = x0 + r;
-  const double scale = __ddiv_rn((double)in_size, (double)out_size);
+  const double scale = (double)in_size / (double)out_size;
   const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = __dmul_rn(2.0, filterscale);       // bicubic: 2.0 * filterscale
-  const double ss = __ddiv_rn(1.0, filterscale);
-  const double center = __dmul_rn(__dadd_rn((double)xx, 0.5), scale);
-  int lo = (int)__dadd_rn(__dsub_rn(center, support), 0.5);
+  const double support = 2.0 * filterscale;                 // bicubic: 2.0 * filterscale
+  const double ss = 1.0 / filterscale;
+  const double center = ((double)xx + 0.5) * scale;
+  int lo = (int)(center - support + 0.5);
   if (lo < 0) lo = 0;
-  int hi = (int)__dadd_rn(__dadd_rn(center, support), 0.5);
+  int hi = (int)(center + support + 0.5);
   if (hi > in_size) hi = in_size;
   int n = hi - lo;
   if (n > ksize) n = ksize;                                   // cannot happen (ksize = 2 ceil(support) + 1 >= hi - lo); keeps every write inside the row
   double ww = 0.0;
-  for (int x = 0; x < n; ++x) ww = __dadd_rn(ww, pil_bicubic(__dmul_rn(__dadd_rn(__dsub_rn((double)(x + lo), center), 0.5), ss)));
+  for (int x = 0; x < n; ++x) ww = ww + pil_bicubic(((double)(x + lo) - center + 0.5) * ss);
   int32_t* row = tab + (long)r * (ksize + 2);
   row[0] = lo - lo_sub; row[1] = n;
   for (int x = 0; x < ksize; ++x) {
     int k = 0;
     if (x < n) {
-      const double w = pil_bicubic(__dmul_rn(__dadd_rn(__dsub_rn((double)(x + lo), center), 0.5), ss));
-      const double v = ww != 0.0 ? __ddiv_rn(w, ww) : w;
-      const double f = __dmul_rn(v, (double)(1 << PIL_BITS));
-      k = v < 0.0 ? (int)__dadd_rn(-0.5, f) : (int)__dadd_rn(0.5, f);
+      const double w = pil_bicubic(((double)(x + lo) - center + 0.5) * ss);
+      const double v = ww != 0.0 ? w / ww : w;
+      const double f = v * (double)(1 << PIL_BITS);
+      k = v < 0.0 ? (int)(-0.5 + f) : (int)(0.5 + f);
     }
     row[2 + x] = k;
   }
