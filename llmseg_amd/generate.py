@@ -25,6 +25,19 @@ from .trainable import IMAGE_TOKEN_INDEX, _Direct
 
 BF16 = torch.bfloat16
 
+# generate()'s quantised weight modes (weight_bits=8, weight_format="mxfp4").  Per mode: the name its persistent buffers and events are kept under; shape and
+# dtype of the (packed rows, scales) of a matrix [N, K]; the `ops` quantiser, called with its own keyword names on the buffers (packed, scale, w_hat); the `ops`
+# GEMM.  (`ops` is looked up at the call, so a wrapped `ops` is seen.)
+QUANT_MODES = {
+    8: dict(name="w8", buffers=lambda N, K: (((N, K), torch.int8), ((N,), torch.float32)),
+            quantize=lambda w, b: ops.quantize_rows_i8(w, q=b[0], scale=b[1], w_hat=b[2]),
+            gemm=lambda a, q, scale, **kw: ops.gemm_w8(a, q, scale, **kw)),
+    "mxfp4": dict(name="mxfp4", buffers=lambda N, K: (((N, K // 2), torch.uint8), ((N, K // 32), torch.uint8)),
+                  quantize=lambda w, b: ops.quantize_rows_mxfp4(w, packed=b[0], scale=b[1], w_hat=b[2]),
+                  gemm=lambda a, packed, scale, **kw: ops.gemm_mxfp4(a, packed, scale, **kw)),
+}
+QUANT_MATRICES = ("qkv", "self_attn.o_proj.weight", "gate_up", "mlp.down_proj.weight")      # the quantised matrices of a layer, under "model.layers.{i}."
+
 
 def pad_prompts(prompts, pad_token_id=0):
     """Prompts of different lengths (1-D id tensors, one <image> token each) -> (input_ids int64 [N, L], attention_mask bool [N, L]) for
@@ -37,6 +50,23 @@ def pad_prompts(prompts, pad_token_id=0):
         ids[i, :t.numel()] = t
         mask[i, :t.numel()] = True
     return ids, mask
+
+
+def _weight_mode(weight_bits, weight_format, fuse_decode):
+    """generate()'s weight arguments, checked -> the weight mode None | 8 | "mxfp4": what the prefill and the decode state are keyed by."""
+    if weight_bits not in (None, 8):
+        raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
+    if weight_bits == 8 and not fuse_decode:
+        raise ValueError("weight_bits=8 needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
+    if weight_format not in (None, "mxfp4"):
+        raise ValueError(f"weight_format must be None or 'mxfp4' (E2M1 elements with one E8M0 scale per 32), got {weight_format!r}")
+    if weight_format is None:
+        return weight_bits
+    if weight_bits is not None:
+        raise ValueError("weight_format='mxfp4' and weight_bits=8 are two quantised modes: pass one of them")
+    if not fuse_decode:
+        raise ValueError("weight_format='mxfp4' needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
+    return weight_format
 
 
 class DecodeState:
@@ -59,7 +89,7 @@ class DecodeState:
         self.qkv_w = None            # per-layer q|k|v weights with the LoRA deltas merged in (fused steps)
         self.bits = None             # weight mode of the captured step: None = bf16 weights, 8 = weight_bits, "mxfp4" = weight_format
         self.ragged = False          # the captured step reads pos_rows (one position per sequence) instead of pos
-        self.w8 = None               # quantised modes: {layer-matrix name: (q int8, scale fp32, w_hat bf16)} of `_quantize_w8`, or (packed uint8, scale uint8, w_hat bf16) of `_quantize_mxfp4`
+        self.qw = None               # quantised modes: {layer-matrix name: (packed rows, scales, w_hat bf16)} of `_quantize_decode_weights`
         self.beam_src = None         # beam search over the never-moved cache: int32 [N, capacity], key t of row r lives in physical row beam_src[r, t]
         self.src_a = self.src_b = None      # beam search: the table at a fixed address (the captured step reads it) and the buffer `ops.beam_step` re-orders it into
 
@@ -132,7 +162,7 @@ class GenerateMixin:
                           k_strides=(st.cap * H, hd, H), v_strides=(st.cap * H, hd, H), o_strides=(H, hd, H), nk_dev=st.pos[1:])
 
     def _decode_linears(self, st):
-        """How a decode step applies a layer's four matrices (W8_MATRICES) on this state's route, chosen once per step:
+        """How a decode step applies a layer's four matrices (QUANT_MATRICES) on this state's route, chosen once per step:
         -> lin(i, name, a, norm=None, swiglu=False, residual=None) = f(a) @ W_name^T (+ residual) of layer i, f = the RMSNorm of weight `norm`, SwiGLU, or nothing."""
         c = self.config.llama
         F = _Direct
@@ -145,12 +175,12 @@ class GenerateMixin:
             return ops.swiglu(a, c.inter) if swiglu else a
 
         if st.bits is not None:                                # int8 or MXFP4 rows; the A-load fusions of the bf16 route for a single sequence are not built for these kernels
-            rows = self._gemm_mxfp4_rows if st.bits == "mxfp4" else self._gemm_w8_rows
+            gemm = QUANT_MODES[st.bits]["gemm"]
 
-            def lin_w8(i, name, a, norm=None, swiglu=False, residual=None):
+            def lin_quantised(i, name, a, norm=None, swiglu=False, residual=None):
                 p = prefix(i)
-                return rows(pre(p, a, norm, swiglu), *st.w8[p + name][:2], residual=residual)
-            return lin_w8
+                return ops.gemm_rows(gemm, pre(p, a, norm, swiglu), *st.qw[p + name][:2], residual=residual)
+            return lin_quantised
 
         members = {"qkv": [f"self_attn.{n}_proj.weight" for n in "qkv"], "gate_up": ["mlp.gate_proj.weight", "mlp.up_proj.weight"]}
 
@@ -188,88 +218,63 @@ class GenerateMixin:
             return out
         return lin
 
-    W8_MATRICES = ("qkv", "self_attn.o_proj.weight", "gate_up", "mlp.down_proj.weight")      # per layer, under "model.layers.{i}."
-
-    def _quantize_w8(self):
-        """weight_bits = 8: the four matrices of every layer (merged q|k|v with the LoRA deltas folded in, o_proj, gate|up, down_proj) as int8 rows
-        with one fp32 scale each, plus W^ = bf16(q * scale) for the prefill, from one `quantize_rows_i8` launch per matrix into persistent
-        buffers (6.5 GB + 13 GB at Llama-7B).  Rebuilt from the CURRENT weights at every call, as the merge is: weights loaded or trained in
-        place can never be stale.  The cost (merge included) is timed with a pair of events: `w8_prepare_ms()`."""
+    def _quantize_decode_weights(self, mode):
+        """A quantised mode of QUANT_MODES: the four matrices of every layer (QUANT_MATRICES: merged q|k|v with the LoRA deltas folded in, o_proj, gate|up,
+        down_proj) as packed rows and scales -- int8 rows with one fp32 scale each, or MXFP4 rows (packed E2M1 nibbles and one E8M0 scale byte per 32 columns) --
+        plus W^ in bf16 for the prefill (bf16(q * scale), or the exact element * 2^e), from one quantiser launch per matrix into persistent buffers kept per
+        mode (6.5 GB or 3.4 GB, + 13 GB at Llama-7B).  Rebuilt from the CURRENT weights at every call, as the merge is: weights loaded or trained in place can
+        never be stale.  The cost (merge included) is timed with a pair of events per mode: `w8_prepare_ms()`, `mxfp4_prepare_ms()`."""
         c = self.config.llama
         F = _Direct
-        ev = self.__dict__.get("_w8_events")
+        fmt = QUANT_MODES[mode]
+        ev = self.__dict__.get(f"_{fmt['name']}_events")
         if ev is None:
-            ev = self.__dict__["_w8_events"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev = self.__dict__[f"_{fmt['name']}_events"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
         merged = self._merge_lora() if c.lora_r > 0 else None
-        bufs = self.__dict__.setdefault("_w8", {})
+        bufs = self.__dict__.setdefault("_" + fmt["name"], {})
         for i in range(c.layers):
             p = f"model.layers.{i}."
             src = (merged[i] if merged is not None else self._wcat(p + "qkv", [p + f"self_attn.{n}_proj.weight" for n in "qkv"], F),
                    self._w(p + "self_attn.o_proj.weight", F),
                    self._wcat(p + "gate_up", [p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], F),
                    self._w(p + "mlp.down_proj.weight", F))
-            for name, w in zip(self.W8_MATRICES, src):
+            for name, w in zip(QUANT_MATRICES, src):
                 b = bufs.get(p + name)
                 if b is None:
-                    b = bufs[p + name] = (torch.empty(w.shape, device=w.device, dtype=torch.int8), torch.empty((w.shape[0],), device=w.device, dtype=torch.float32),
-                                          torch.empty_like(w))
-                ops.quantize_rows_i8(w, q=b[0], scale=b[1], w_hat=b[2])
+                    (ps, pd), (ss, sd) = fmt["buffers"](*w.shape)
+                    b = bufs[p + name] = (torch.empty(ps, device=w.device, dtype=pd), torch.empty(ss, device=w.device, dtype=sd), torch.empty_like(w))
+                fmt["quantize"](w, b)
         ev[1].record()
         return bufs
 
-    def w8_prepare_ms(self):
-        """Device time of the last `generate(weight_bits=8)` call's LoRA merge + quantisation (waits for that work to finish)."""
-        ev = self.__dict__["_w8_events"]
+    def _prepare_ms(self, mode):
+        ev = self.__dict__[f"_{QUANT_MODES[mode]['name']}_events"]
         ev[1].synchronize()
         return ev[0].elapsed_time(ev[1])
+
+    def _decode_weights(self, mode):
+        return {k: (b[0], b[1]) for k, b in self.__dict__["_" + QUANT_MODES[mode]["name"]].items()}
+
+    def w8_prepare_ms(self):
+        """Device time of the last `generate(weight_bits=8)` call's LoRA merge + quantisation (waits for that work to finish)."""
+        return self._prepare_ms(8)
 
     def decode_weights_i8(self):
         """{layer-matrix name: (q int8 [N, K], scale fp32 [N])} of the last `generate(weight_bits=8)` call: names are "model.layers.{i}." +
         "qkv" (merged q|k|v), "self_attn.o_proj.weight", "gate_up" (gate|up) and "mlp.down_proj.weight"."""
-        return {k: (b[0], b[1]) for k, b in self.__dict__["_w8"].items()}
-
-    def _quantize_mxfp4(self):
-        """weight_format = "mxfp4": the four matrices of every layer (W8_MATRICES, q|k|v with the LoRA deltas merged in) as MXFP4 rows -- packed E2M1 nibbles
-        and one E8M0 scale byte per 32 columns -- plus W^ = element * 2^e in bf16 (exact) for the prefill, from one `quantize_rows_mxfp4` launch per matrix into
-        persistent buffers (3.4 GB + 13 GB at Llama-7B).  Rebuilt from the CURRENT weights at every call, as the int8 mode does.  The cost (merge included) is
-        timed with a pair of events: `mxfp4_prepare_ms()`."""
-        c = self.config.llama
-        F = _Direct
-        ev = self.__dict__.get("_mxfp4_events")
-        if ev is None:
-            ev = self.__dict__["_mxfp4_events"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-        merged = self._merge_lora() if c.lora_r > 0 else None
-        bufs = self.__dict__.setdefault("_mxfp4", {})
-        for i in range(c.layers):
-            p = f"model.layers.{i}."
-            src = (merged[i] if merged is not None else self._wcat(p + "qkv", [p + f"self_attn.{n}_proj.weight" for n in "qkv"], F),
-                   self._w(p + "self_attn.o_proj.weight", F),
-                   self._wcat(p + "gate_up", [p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], F),
-                   self._w(p + "mlp.down_proj.weight", F))
-            for name, w in zip(self.W8_MATRICES, src):
-                b = bufs.get(p + name)
-                if b is None:
-                    N, K = w.shape
-                    b = bufs[p + name] = (torch.empty((N, K // 2), device=w.device, dtype=torch.uint8), torch.empty((N, K // 32), device=w.device, dtype=torch.uint8),
-                                          torch.empty_like(w))
-                ops.quantize_rows_mxfp4(w, packed=b[0], scale=b[1], w_hat=b[2])
-        ev[1].record()
-        return bufs
+        return self._decode_weights(8)
 
     def mxfp4_prepare_ms(self):
         """Device time of the last `generate(weight_format="mxfp4")` call's LoRA merge + quantisation (waits for that work to finish)."""
-        ev = self.__dict__["_mxfp4_events"]
-        ev[1].synchronize()
-        return ev[0].elapsed_time(ev[1])
+        return self._prepare_ms("mxfp4")
 
     def decode_weights_mxfp4(self):
         """{layer-matrix name: (packed uint8 [N, K / 2], scale uint8 [N, K / 32])} of the last `generate(weight_format="mxfp4")` call; the names are
         `decode_weights_i8`'s."""
-        return {k: (b[0], b[1]) for k, b in self.__dict__["_mxfp4"].items()}
+        return self._decode_weights("mxfp4")
 
-    def _prefill_w8(self, embeds, key_mask_u8, w8, kv_out):
+    def _prefill_quantised(self, embeds, key_mask_u8, qw, kv_out):
         """The prompt through the decoder stack of the QUANTISED model: the no-grad kernel sequence of `_llama` on W^ (entry [2] of every matrix: bf16(q * scale)
         of the int8 mode, the exact element * 2^e of MXFP4), so that prefill and decode steps run one model (the one a cache-free forward on the dequantised
         state dict runs).  -> final-norm hidden [N, T, H]."""
@@ -281,37 +286,14 @@ class GenerateMixin:
         for i in range(c.layers):
             p = f"model.layers.{i}."
             h = F.norm(x, self._w(p + "input_layernorm.weight", F), None, c.eps, True)
-            qkv = ops.gemm(h, w8[p + "qkv"][2])
+            qkv = ops.gemm(h, qw[p + "qkv"][2])
             a = F.rope_attn(qkv, rope, N, T, c.heads, c.head_dim, True, key_mask_u8)
             kv_out(i, qkv)                                     # qkv now holds the rotated K and V
-            x = ops.gemm(a, w8[p + "self_attn.o_proj.weight"][2], residual=x)
+            x = ops.gemm(a, qw[p + "self_attn.o_proj.weight"][2], residual=x)
             h = F.norm(x, self._w(p + "post_attention_layernorm.weight", F), None, c.eps, True)
-            gu = ops.gemm(h, w8[p + "gate_up"][2])
-            x = ops.gemm(ops.swiglu(gu, c.inter), w8[p + "mlp.down_proj.weight"][2], residual=x)
+            gu = ops.gemm(h, qw[p + "gate_up"][2])
+            x = ops.gemm(ops.swiglu(gu, c.inter), qw[p + "mlp.down_proj.weight"][2], residual=x)
         return F.norm(x, self._w("model.norm.weight", F), None, c.eps, True).view(N, T, H)
-
-    @staticmethod
-    def _gemm_w8_rows(a, q, scale, residual=None):
-        """`ops.gemm_w8` (at most 8 rows a call) on any number of rows: up to 8 rows it IS that call; more rows (prompts x beams) go in chunks of 8, each
-        streaming the weights again."""
-        M = a.shape[0]
-        if M <= 8:
-            return ops.gemm_w8(a, q, scale, residual=residual)
-        out = torch.empty((M, q.shape[0]), device=a.device, dtype=BF16)
-        for r in range(0, M, 8):
-            ops.gemm_w8(a[r:r + 8], q, scale, residual=None if residual is None else residual[r:r + 8], out=out[r:r + 8])
-        return out
-
-    @staticmethod
-    def _gemm_mxfp4_rows(a, packed, scale, residual=None):
-        """`ops.gemm_mxfp4` (at most 8 rows a call) on any number of rows, in chunks of 8 as `_gemm_w8_rows`."""
-        M = a.shape[0]
-        if M <= 8:
-            return ops.gemm_mxfp4(a, packed, scale, residual=residual)
-        out = torch.empty((M, packed.shape[0]), device=a.device, dtype=BF16)
-        for r in range(0, M, 8):
-            ops.gemm_mxfp4(a[r:r + 8], packed, scale, residual=None if residual is None else residual[r:r + 8], out=out[r:r + 8])
-        return out
 
     def _decode_step(self, st, use_graph=True):
         """Run one decode step; from the second step of a state on, replay it from a hipGraph (captured once per (N, capacity): a step is
@@ -358,11 +340,11 @@ class GenerateMixin:
             st.k[i, ::rows, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
             st.v[i, ::rows, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
         if weight_bits is None:
-            st.w8 = None
+            st.qw = None
             hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
         else:
-            st.w8 = self._quantize_mxfp4() if weight_bits == "mxfp4" else self._quantize_w8()
-            hidden_p = self._prefill_w8(embeds, plan.key_mask, st.w8, keep_kv)
+            st.qw = self._quantize_decode_weights(weight_bits)
+            hidden_p = self._prefill_quantised(embeds, plan.key_mask, st.qw, keep_kv)
         ragged = attention_mask is not None or rows > 1       # beams: every row at its own device-side position (they are equal; the per-row kernels read them)
         if fused != st.fused or weight_bits != st.bits or ragged != st.ragged:
             st.fused, st.bits, st.ragged, st.graph, st.warm = fused, weight_bits, ragged, None, False      # a different kernel sequence: capture again
@@ -491,23 +473,10 @@ class GenerateMixin:
                                          tuple(uniforms.shape) != (input_ids.shape[0], max_new_tokens)):
                 raise ValueError(f"uniforms must be an fp32 tensor [N, max_new_tokens] = {(input_ids.shape[0], max_new_tokens)}, got "
                                  f"{getattr(uniforms, 'dtype', type(uniforms))} {tuple(getattr(uniforms, 'shape', ()))}")
-        if weight_bits not in (None, 8):
-            raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
-        if weight_bits == 8 and not fuse_decode:
-            raise ValueError("weight_bits=8 needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
-        if weight_format not in (None, "mxfp4"):
-            raise ValueError(f"weight_format must be None or 'mxfp4' (E2M1 elements with one E8M0 scale per 32), got {weight_format!r}")
-        if weight_format is not None:
-            if weight_bits is not None:
-                raise ValueError("weight_format='mxfp4' and weight_bits=8 are two quantised modes: pass one of them")
-            if not fuse_decode:
-                raise ValueError("weight_format='mxfp4' needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
-        mode = weight_bits if weight_format is None else weight_format      # None | 8 | "mxfp4": what the prefill and the decode state are keyed by
+        mode = _weight_mode(weight_bits, weight_format, fuse_decode)
         if num_beams >= 2:
             if not defaults:
                 raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True")
-            if weight_bits not in (None, 8):
-                raise ValueError(f"weight_bits must be None (bf16 weights) or 8 (int8 rows with per-row scales), got {weight_bits!r}")
             return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, mode, attention_mask, num_beams,
                                         float(length_penalty), early_stopping, return_beam_scores, beam_cache, _beam_trace)
         lens = None                                            # prompt lengths L_i on the host, ragged calls only

@@ -184,15 +184,14 @@ def quantize_rows_i8(w, want_hat=False, q=None, scale=None, w_hat=None):
     return (q, scale, w_hat) if w_hat is not None else (q, scale)
 
 
-def gemm_w8(a, q, scale, residual=None, out=None, out_f32=False):
-    """out[M, N] = residual + scale[n] * (a [M, K] bf16 @ q [N, K] int8 ^T), M <= 8: the decode step's weight stream on int8 rows with one fp32
-    scale each (`quantize_rows_i8`).  fp32 accumulation, the scale applied once to the finished sum; out bf16, or fp32 with out_f32."""
+def _gemm_quantised(a, q, scale, residual, out, out_f32, scale_shape, args, entry):
+    """The body of `gemm_w8` / `gemm_mxfp4`, which have checked the dtypes and the packed row length of their format: q the packed rows [N, ..], scale of
+    shape scale_shape(N, K); `args` the format's argument struct, `entry` the library call's name without the prefix."""
     _req(a)
-    assert a.dim() == 2 and q.dim() == 2 and a.stride(1) == 1 and q.stride(1) == 1 and q.is_cuda and q.dtype == torch.int8
+    assert q.dim() == 2 and a.stride(1) == 1 and q.stride(1) == 1 and q.is_cuda and scale.is_cuda
     M, K = a.shape
     N = q.shape[0]
-    assert q.shape[1] == K and M <= 8, (a.shape, q.shape)
-    assert scale.is_cuda and scale.dtype == torch.float32 and scale.shape == (N,) and scale.is_contiguous()
+    assert M <= 8 and scale.shape == scale_shape(N, K) and scale.stride(-1) == 1, (a.shape, q.shape, scale.shape)
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else BF16)
     else:
@@ -200,11 +199,20 @@ def gemm_w8(a, q, scale, residual=None, out=None, out_f32=False):
     assert out.shape == (M, N) and out.stride(1) == 1 and (out_f32 or out.dtype == BF16)
     if residual is not None:
         assert _req(residual).shape == (M, N) and residual.stride(1) == 1
-    g = _lib.GemmW8Args(A=a.data_ptr(), Q=q.data_ptr(), scale=scale.data_ptr(), residual=None if residual is None else residual.data_ptr(), C=out.data_ptr(),
-                        M=M, N=N, K=K, lda=a.stride(0), ldq=q.stride(0), ldc=out.stride(0), ldr=0 if residual is None else residual.stride(0),
-                        out_f32=1 if out_f32 else 0)
-    _lib.check(_lib.load().llmseg_gemm_w8(C.byref(g), _stream()), "gemm_w8")
+    g = args(A=a.data_ptr(), Q=q.data_ptr(), scale=scale.data_ptr(), residual=None if residual is None else residual.data_ptr(), C=out.data_ptr(),
+             M=M, N=N, K=K, lda=a.stride(0), ldq=q.stride(0), ldc=out.stride(0), ldr=0 if residual is None else residual.stride(0),
+             out_f32=1 if out_f32 else 0)
+    if scale.dim() == 2:                                     # a scale per block, not per row: the struct has its row pitch
+        g.lds = scale.stride(0)
+    _lib.check(getattr(_lib.load(), "llmseg_" + entry)(C.byref(g), _stream()), entry)
     return out
+
+
+def gemm_w8(a, q, scale, residual=None, out=None, out_f32=False):
+    """out[M, N] = residual + scale[n] * (a [M, K] bf16 @ q [N, K] int8 ^T), M <= 8: the decode step's weight stream on int8 rows with one fp32
+    scale each (`quantize_rows_i8`).  fp32 accumulation, the scale applied once to the finished sum; out bf16, or fp32 with out_f32."""
+    assert a.dim() == 2 and q.dtype == torch.int8 and scale.dtype == torch.float32 and q.shape[1:] == a.shape[1:], (a.shape, q.shape)
+    return _gemm_quantised(a, q, scale, residual, out, out_f32, lambda N, K: (N,), _lib.GemmW8Args, "gemm_w8")
 
 
 def quantize_rows_mxfp4(w, want_hat=False, packed=None, scale=None, w_hat=None):
@@ -234,23 +242,19 @@ def gemm_mxfp4(a, packed, scale, residual=None, out=None, out_f32=False):
     """out[M, N] = residual + a [M, K] bf16 @ w_hat [N, K] ^T, M <= 8, with w_hat decoded on the fly from MXFP4 rows (`quantize_rows_mxfp4`: packed uint8
     [N, K / 2], scale uint8 [N, K / 32]): the decode step's weight stream at 4.25 bits per weight.  The products are exact in fp32 and accumulated in fp32;
     out bf16, or fp32 with out_f32."""
-    _req(a)
-    assert a.dim() == 2 and packed.dim() == 2 and scale.dim() == 2 and a.stride(1) == 1 and packed.stride(1) == 1 and scale.stride(1) == 1
-    assert packed.is_cuda and packed.dtype == torch.uint8 and scale.is_cuda and scale.dtype == torch.uint8
-    M, K = a.shape
-    N = packed.shape[0]
-    assert K % 32 == 0 and packed.shape[1] == K // 2 and scale.shape == (N, K // 32) and M <= 8, (a.shape, packed.shape, scale.shape)
-    if out is None:
-        out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else BF16)
-    else:
-        out_f32 = out.dtype == torch.float32
-    assert out.shape == (M, N) and out.stride(1) == 1 and (out_f32 or out.dtype == BF16)
-    if residual is not None:
-        assert _req(residual).shape == (M, N) and residual.stride(1) == 1
-    g = _lib.GemmMxfp4Args(A=a.data_ptr(), Q=packed.data_ptr(), scale=scale.data_ptr(), residual=None if residual is None else residual.data_ptr(), C=out.data_ptr(),
-                           M=M, N=N, K=K, lda=a.stride(0), ldq=packed.stride(0), lds=scale.stride(0), ldc=out.stride(0),
-                           ldr=0 if residual is None else residual.stride(0), out_f32=1 if out_f32 else 0)
-    _lib.check(_lib.load().llmseg_gemm_mxfp4(C.byref(g), _stream()), "gemm_mxfp4")
+    assert a.dim() == 2 and a.shape[1] % 32 == 0 and packed.dtype == torch.uint8 and scale.dtype == torch.uint8 and packed.shape[1:] == (a.shape[1] // 2,), (a.shape, packed.shape)
+    return _gemm_quantised(a, packed, scale, residual, out, out_f32, lambda N, K: (N, K // 32), _lib.GemmMxfp4Args, "gemm_mxfp4")
+
+
+def gemm_rows(gemm, a, q, scale, residual=None):
+    """`gemm` = `gemm_w8` or `gemm_mxfp4` (at most 8 rows a call) on any number of rows: up to 8 rows it IS that call; more rows (prompts x beams) go in
+    chunks of 8, each streaming the weights again."""
+    M = a.shape[0]
+    if M <= 8:
+        return gemm(a, q, scale, residual=residual)
+    out = torch.empty((M, q.shape[0]), device=a.device, dtype=BF16)
+    for r in range(0, M, 8):
+        gemm(a[r:r + 8], q, scale, residual=None if residual is None else residual[r:r + 8], out=out[r:r + 8])
     return out
 
 

@@ -1,4 +1,4 @@
-"""MXFP4 weight-only decode (llmseg_amd/csrc/mxfp4.hip, generate(weight_format="mxfp4")): a torch restatement of the public quantiser arithmetic, hand-built
+"""MXFP4 weight-only decode (llmseg_amd/csrc/decode_gemm.hip, generate(weight_format="mxfp4")): a torch restatement of the public quantiser arithmetic, hand-built
 blocks with known codes, a case table for `llmseg_gemm_mxfp4` with fp64 references, PER-ELEMENT bounds, an fp32 emulation of what the kernel rounds and mutants
 (fp64 results of slightly wrong problems) the bounds must reject, and the state dicts of the generation tests.
 
@@ -143,7 +143,7 @@ def quant_input(N, K, pad):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- the GEMM's table
-# The kernels (llmseg_amd/csrc/mxfp4.hip).  M <= 2, the vector-ALU kernel: a wave owns 4 packed rows and walks K in steps of STEP = 2048 columns (a lane's
+# The kernels (llmseg_amd/csrc/decode_gemm.hip).  M <= 2, the vector-ALU kernel: a wave owns 4 packed rows and walks K in steps of STEP = 2048 columns (a lane's
 # 16-byte load is 32 weights); at N <= KSPLIT_N and K >= KSPLIT_K the 4 waves of a workgroup share their rows and take the steps in turn (wave v: steps v,
 # v + 4, ...).  M >= MFMA_ROWS, the matrix-core kernel: a wave owns 16 rows, its unit is UNIT = 128 columns, the NW waves of a workgroup take the units in
 # turn (NW = 16 at N <= MFMA_WIDE_N, else 4): a workgroup's step is NW * UNIT = 2048 or 512 columns.

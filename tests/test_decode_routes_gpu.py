@@ -1,7 +1,8 @@
 """GPU: every route of generate()'s decode step issues the kernel sequence it is known to issue, and that sequence is a pure, replayable one.
   * library launches (`llmseg_launch_count`) of ONE eager decode step on each route, against the table LAUNCHES below.  The table was filled by running
     `route_launches` -- the counting code of this file, unchanged -- on the commit BEFORE the three step bodies of generate.py were folded into one, never
-    on the folded code: a route that gains or loses a launch no longer matches it.
+    on the folded code: a route that gains or loses a launch no longer matches it.  (The mxfp4 routes: on the commit before the int8 and MXFP4 decode
+    GEMMs and their host paths were folded into one.)
   * `use_graph=True` and `use_graph=False` return the same bits on every route (sequences, hidden states, beam values): a step body that allocates, branches
     or reads host state differently between its eager run and its capture does not.
 The model is the tiny head_dim-128 configuration of tests/test_beam_gpu.py (LoRA rank 8, so that the unfused route runs its LoRA launches)."""
@@ -25,6 +26,9 @@ ROUTES = {
     "ragged_n2": (2, dict(ragged=True)),
     "w8_n1": (1, dict(weight_bits=8)),
     "w8_n9": (9, dict(weight_bits=8)),                       # more than 8 rows: `ops.gemm_w8` in chunks of 8
+    "mxfp4_n1": (1, dict(weight_format="mxfp4")),            # the vector-ALU stream kernel
+    "mxfp4_n3": (3, dict(weight_format="mxfp4")),            # from 3 rows: the matrix-core kernel
+    "mxfp4_n9": (9, dict(weight_format="mxfp4")),            # `ops.gemm_mxfp4` in chunks of 8 (8 rows on the matrix cores, 1 on the stream kernel)
     "beams2_indirect": (2, dict(num_beams=2, beam_cache="indirect")),
     "beams2_copy": (2, dict(num_beams=2, beam_cache="copy")),
 }
@@ -36,6 +40,9 @@ LAUNCHES = {
     "ragged_n2": 20,
     "w8_n1": 20,
     "w8_n9": 28,
+    "mxfp4_n1": 20,
+    "mxfp4_n3": 20,
+    "mxfp4_n9": 28,
     "beams2_indirect": 20,
     "beams2_copy": 20,
 }

@@ -1,4 +1,4 @@
-"""int8 weight-only decode (llmseg_amd/csrc/quant.hip, generate(weight_bits=8)): a torch restatement of the public quantiser arithmetic, hand-built rows,
+"""int8 weight-only decode (llmseg_amd/csrc/decode_gemm.hip, generate(weight_bits=8)): a torch restatement of the public quantiser arithmetic, hand-built rows,
 a case table for `llmseg_gemm_w8` with fp64 references, PER-ELEMENT bounds, an fp32 emulation of what the kernel rounds and mutants (fp64 results of slightly
 wrong problems) the bounds must reject, and the state dicts of the generation test.
 
@@ -91,7 +91,7 @@ def quant_input(N, K, pad):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- the GEMM's table
-# The kernel (llmseg_amd/csrc/quant.hip): a wave owns 4 q rows and walks K in steps of 1024 columns (rows templates 4 and 8, and wherever the workgroup's waves
+# The kernel (gemm_stream_kernel<I8, ..>, llmseg_amd/csrc/decode_gemm.hip): a wave owns 4 q rows and walks K in steps of 1024 columns (rows templates 4 and 8, and wherever the workgroup's waves
 # split K) or 2048 (templates 1 and 2); at N <= 8192 and K >= 4096 the 4 waves of a workgroup share their rows and the workgroup's step is 4096 (resp. 4 x 1024).
 W8_N = (1, 3, 4, 5, 15, 16, 17, 37)
 W8_K = (16, 1008, 1024, 1040, 2032, 2048, 2064, 3056, 3072, 3088, 4080, 4096, 4112, 6128, 6144, 6160, 8176, 8192, 8208)
