@@ -17,6 +17,7 @@ HF greedy-search rules restated from `transformers==4.29.0 generation/utils.py::
 `pad_token_id`, a row finishes on `eos_token_id`, the loop stops when all rows are finished or `max_new_tokens` tokens were added.
 """
 import math
+import types
 
 import torch
 
@@ -67,6 +68,215 @@ def _weight_mode(weight_bits, weight_format, fuse_decode):
     if not fuse_decode:
         raise ValueError("weight_format='mxfp4' needs fuse_decode=True: the LoRA deltas are merged into q|k|v before quantisation")
     return weight_format
+
+
+def _check_controls(model, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens, num_beams):
+    """generate()'s logits controls, checked -> None with all four at their defaults (no logits-processor launch), else the four by name, suppress_tokens as a list."""
+    if repetition_penalty == 1.0 and no_repeat_ngram_size == 0 and min_new_tokens == 0 and suppress_tokens is None:
+        return None
+    if isinstance(repetition_penalty, bool) or not (isinstance(repetition_penalty, (int, float)) and math.isfinite(repetition_penalty) and repetition_penalty > 0):
+        raise ValueError(f"repetition_penalty must be a finite number > 0 (1 = off), got {repetition_penalty!r}")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+        if not (isinstance(v, int) and not isinstance(v, bool) and 0 <= v < 2 ** 31):
+            raise ValueError(f"{name} must be an integer >= 0 (0 = off), got {v!r}")
+    if min_new_tokens > 0 and eos_token_id is None:
+        raise ValueError("min_new_tokens needs an eos_token_id: it bans that token until enough tokens were emitted")
+    if min_new_tokens > max_new_tokens:
+        raise ValueError(f"min_new_tokens = {min_new_tokens} exceeds max_new_tokens = {max_new_tokens}")
+    if suppress_tokens is not None:
+        vocab = model.config.llama.vocab
+        try:
+            suppress_tokens = list(suppress_tokens)
+        except TypeError:
+            raise ValueError(f"suppress_tokens must be a sequence of integers in [0, {vocab}), got {suppress_tokens!r}") from None
+        if not suppress_tokens or not all(isinstance(t, int) and not isinstance(t, bool) and 0 <= t < vocab for t in suppress_tokens):
+            raise ValueError(f"suppress_tokens must be a non-empty sequence of integers in [0, vocab = {vocab}), got {suppress_tokens!r}")
+    if isinstance(num_beams, int) and num_beams >= 2:
+        raise ValueError("repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens with num_beams >= 2 are out of scope: beam search applies "
+                         "processors to the log-softmax, another rule")
+    return dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)
+
+
+def _check_beams(model, num_beams, length_penalty, early_stopping, return_beam_scores, beam_cache, trace, do_sample, fuse_decode):
+    """generate()'s beam arguments, checked: num_beams == 1 takes none of the others; what num_beams >= 2 does not go with is refused here."""
+    if not (isinstance(num_beams, int) and not isinstance(num_beams, bool) and num_beams >= 1):
+        raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
+    if beam_cache not in ("indirect", "copy"):
+        raise ValueError(f"beam_cache must be 'indirect' or 'copy', got {beam_cache!r}")
+    if not isinstance(early_stopping, bool):
+        raise ValueError(f"early_stopping must be True or False ('never' is out of scope), got {early_stopping!r}")
+    if isinstance(length_penalty, bool) or not (isinstance(length_penalty, (int, float)) and math.isfinite(length_penalty)):
+        raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
+    if num_beams == 1 and not (length_penalty == 1.0 and early_stopping is False and not return_beam_scores and beam_cache == "indirect" and trace is None):
+        raise ValueError("length_penalty, early_stopping, return_beam_scores and beam_cache need num_beams >= 2")
+    if num_beams >= 2:
+        if do_sample:
+            raise ValueError("do_sample with num_beams >= 2 (beam sampling) is out of scope")
+        if not fuse_decode:
+            raise ValueError("num_beams >= 2 needs fuse_decode=True (the beam-indexed cache is built into the fused decode step only)")
+        if model.config.llama.head_dim != 128:
+            raise ValueError(f"num_beams >= 2 needs head_dim 128, got {model.config.llama.head_dim}: the two-launch route is out of scope")
+        if num_beams > 16 or 2 * num_beams > model.config.llama.vocab:
+            raise ValueError(f"num_beams must be <= 16 and 2 * num_beams <= vocab = {model.config.llama.vocab}, got {num_beams}")
+
+
+def _check_sampling(do_sample, temperature, top_k, top_p, seed, uniforms, return_logprobs, input_ids, max_new_tokens):
+    """generate()'s sampling arguments, checked -> None for the arg-max (which takes none of them), else the arguments by name."""
+    if not do_sample:
+        if not (temperature == 1.0 and top_k == 0 and top_p == 1.0 and seed is None and uniforms is None and not return_logprobs):
+            raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True (greedy decoding takes none of them)")
+        return None
+    if not (isinstance(temperature, (int, float)) and math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    if not (isinstance(top_k, int) and not isinstance(top_k, bool) and 0 <= top_k < 2 ** 31):
+        raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k!r}")
+    if not (isinstance(top_p, (int, float)) and 0 < top_p <= 1):
+        raise ValueError(f"top_p must be in (0, 1] (1 = off), got {top_p!r}")
+    if seed is not None and uniforms is not None:
+        raise ValueError("pass seed= or uniforms=, not both")
+    if uniforms is not None and (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (input_ids.shape[0], max_new_tokens)):
+        raise ValueError(f"uniforms must be an fp32 tensor [N, max_new_tokens] = {(input_ids.shape[0], max_new_tokens)}, got "
+                         f"{getattr(uniforms, 'dtype', type(uniforms))} {tuple(getattr(uniforms, 'shape', ()))}")
+    return dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, uniforms=uniforms, return_logprobs=return_logprobs)
+
+
+def _row_prompts(model, input_ids, attention_mask, fuse_decode, fill, controls, max_new_tokens):
+    """The row loop's prompts, checked where the trimmed mask is known -> (input_ids, attention_mask, lens): trimmed to the longest prompt, the padding set to `fill`,
+    lens = the prompt lengths L_i on the host; (input_ids, None, None) on the uniform route."""
+    lens = None
+    if attention_mask is not None:
+        input_ids, attention_mask, lens = model._ragged_prompts(input_ids, attention_mask)
+    if lens is not None:
+        if not fuse_decode:
+            raise ValueError("prompts of different lengths need fuse_decode=True (the per-row positions are built into the fused decode step only)")
+        if model.config.llama.head_dim != 128:
+            raise ValueError(f"prompts of different lengths need head_dim 128, got {model.config.llama.head_dim}: per-row key counts for the two-launch "
+                             "route (llmseg_rope_kv_append + llmseg_attn_fwd) are out of scope")
+        input_ids = torch.where(attention_mask.to(input_ids.device), input_ids, torch.full_like(input_ids, fill))
+    if controls is not None and input_ids.shape[1] + max_new_tokens > ops.LOGITS_HIST_CAP:
+        raise ValueError(f"repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens keep a history of prompt + max_new_tokens = "
+                         f"{input_ids.shape[1]} + {max_new_tokens} ids per row: more than the cap of {ops.LOGITS_HIST_CAP}")
+    return input_ids, attention_mask, lens
+
+
+def _make_pick(ids, lens, max_new_tokens, eos_token_id, pad_token_id, sampling, controls):
+    """The row loop's pick, decided once per call from the checked arguments -> (pick, live): pick(logits [N, V], step) = the next token of every row (int64 [N]) by the arg-max,
+    or by `ops.sample_tokens` (`sampling`), after the `ops.logits_process` launch if there are `controls`; a finished row emits pad_token_id.  live.unfinished (int64 [N]) is 0
+    for the finished rows; live.logprobs holds what `ops.sample_tokens` returned at every step; live.last is the token the history has yet to take in."""
+    dev, (N, L) = ids.device, ids.shape
+    live = types.SimpleNamespace(unfinished=torch.ones((N,), dtype=torch.int64, device=dev), logprobs=[], last=None)
+    if sampling is None:
+        def pick(logits, step):
+            nxt = logits.float().argmax(-1)
+            if eos_token_id is not None:
+                nxt = nxt * live.unfinished + pad_token_id * (1 - live.unfinished)
+                live.unfinished = live.unfinished * (nxt != eos_token_id).long()
+            return nxt
+    else:
+        uniforms = sampling["uniforms"]
+        if uniforms is None:
+            gen = None if sampling["seed"] is None else torch.Generator(device=dev).manual_seed(int(sampling["seed"]))
+            uniforms = torch.rand((N, max_new_tokens), device=dev, dtype=torch.float32, generator=gen)
+        u_steps = uniforms.to(dev).t().contiguous()            # [max_new_tokens, N]: step s reads one contiguous row
+
+        def pick(logits, step):                                # one launch: the pick, pad for finished rows and the update of `unfinished`
+            nxt, lp, _, _ = ops.sample_tokens(logits, sampling["temperature"], sampling["top_k"], sampling["top_p"], u_steps[step], eos_token_id=eos_token_id,
+                                              pad_token_id=pad_token_id, unfinished=live.unfinished, want_logprob=sampling["return_logprobs"])
+            live.logprobs.append(lp)
+            return nxt
+    if controls is None:
+        return pick, live
+    hist = torch.zeros((N, L + max_new_tokens), dtype=torch.int64, device=dev)      # each row's history at a fixed address: its own prompt, left-aligned
+    hist[:, :L] = ids
+    hist_len = (torch.full((N,), L, dtype=torch.int32) if lens is None else lens.to(torch.int32)).to(dev)
+    suppress = None if controls["suppress_tokens"] is None else torch.tensor(controls["suppress_tokens"], dtype=torch.int32, device=dev)
+
+    def processed_pick(logits, step):                          # one launch: the token just picked joins the history, then the processors rewrite the step's logits in place
+        logits = ops.logits_process(logits, hist, hist_len, append=live.last, repetition_penalty=controls["repetition_penalty"], suppress=suppress,
+                                    no_repeat_ngram_size=controls["no_repeat_ngram_size"], ban_token=eos_token_id if step < controls["min_new_tokens"] else None)
+        live.last = pick(logits, step)
+        return live.last
+    return processed_pick, live
+
+
+def _uniform_rows(st, hidden_p, lm_w, max_new_tokens):
+    """The row loop's layout when every prompt has the same length -> (the first logits, store(st.hidden, n_new), pack(seqs, n_new) -> (sequences, hidden)): one position for
+    all rows (st.pos), one column of `hidden` per step."""
+    N, T, H = hidden_p.shape
+    st.pos.copy_(torch.tensor([T, T + 1], dtype=torch.int32))
+    hidden = torch.empty((N, T + max_new_tokens - 1, H), device=hidden_p.device, dtype=BF16)
+    hidden[:, :T] = hidden_p
+
+    def store(h, n_new):
+        hidden[:, T + n_new - 1] = h
+    return ops.gemm(hidden_p[:, -1].contiguous(), lm_w), store, lambda seqs, n_new: (torch.cat(seqs, 1), hidden[:, :T + n_new - 1])      # only the last position's logits are needed
+
+
+def _ragged_rows(st, hidden_p, lm_w, max_new_tokens, lens, Pn, fill):
+    """The same three when the prompts differ in length (lens [N], on the host): a position per row (st.pos_rows), both results packed per row, left-aligned."""
+    N, T, H = hidden_p.shape
+    dev = hidden_p.device
+    t_rows = (lens - 1 + Pn).to(dev)                           # T_i: row i's prefill length = the position of its first fed token
+    st.pos_rows.copy_(t_rows.to(torch.int32))
+    hidden = torch.zeros((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
+    own = torch.arange(T, device=dev)[None, :] < t_rows[:, None]
+    hidden[:, :T] = torch.where(own[:, :, None], hidden_p, torch.zeros_like(hidden_p))
+    last = torch.arange(N, device=dev) * T + t_rows - 1                                # each row's own last prompt position
+    logits = ops.gemm(ops.gather_rows(hidden_p.reshape(N * T, H), last), lm_w)
+    slot = torch.arange(N, device=dev) * hidden.shape[1] + t_rows - 1                    # flat row of `hidden` that holds each sequence's newest state
+
+    def pack(seqs, n_new):                                     # row i: prompt, new tokens, fill
+        out = torch.cat([seqs[0], torch.full((N, n_new), fill, dtype=torch.int64, device=dev)], 1)
+        out.scatter_(1, lens.to(dev)[:, None] + torch.arange(n_new, device=dev)[None, :], torch.cat(seqs[1:], 1))
+        return out, hidden[:, :T + n_new - 1]
+    return logits, lambda h, n_new: hidden.view(-1, H).index_copy_(0, slot.add_(1), h), pack
+
+
+class BeamBook:
+    """The host's book of a beam search over N prompts of B beams, in plain Python: per prompt the pool of its B best hypotheses (value, kind, step, slot), the "done"
+    rule, the live beams that join at the end, and the back-trace of the winner through the parents."""
+
+    def __init__(self, N, B, length_penalty, early_stopping, eos_token_id):
+        self.N, self.B, self.lp, self.early, self.eos = N, B, length_penalty, early_stopping, eos_token_id
+        self.done, self.pools = [False] * N, [[] for _ in range(N)]
+
+    @staticmethod
+    def add(pool, B, hyp):
+        """Hugging Face's BeamHypotheses.add: keep the B best by value; a newcomer enters a full pool only when it beats the worst, which then leaves."""
+        if len(pool) < B:
+            pool.append(hyp)
+        elif hyp[0] > min(h[0] for h in pool):
+            worst = min(range(len(pool)), key=lambda i: pool[i][0])
+            pool[worst] = hyp
+
+    def step(self, step, step_best, fin_count, fin_parent, fin_score):
+        """The record of pick `step` (lists [N], [N], [N][B], [N][B]): the eos candidates become hypotheses of step + 1 tokens, then the done rule."""
+        g = step + 1
+        for n in range(self.N):
+            if self.done[n]:
+                continue
+            for k in range(fin_count[n]):
+                self.add(self.pools[n], self.B, (fin_score[n][k] / g ** self.lp, "eos", step, fin_parent[n][k]))
+            if len(self.pools[n]) >= self.B and (self.early or min(h[0] for h in self.pools[n]) >= step_best[n] / g ** self.lp):
+                self.done[n] = True
+
+    def finish(self, last_scores, tokens, parents):
+        """last_scores [N * B] of the last pick; tokens, parents [steps][N * B] of every pick -> per prompt (the winner's tokens, its value, the flat rows
+        t * N * B + n * B + slot of the steps' hidden states for every token of the winner but the last: the state of each FED token)."""
+        steps, B, R = len(tokens), self.B, self.N * self.B
+        winners = []
+        for n in range(self.N):
+            if not self.done[n]:                               # a prompt that is not done: its live beams are hypotheses of `steps` tokens
+                for i in range(B):
+                    self.add(self.pools[n], B, (last_scores[n * B + i] / steps ** self.lp, "live", steps - 1, i))
+            value, kind, s, slot = max(self.pools[n], key=lambda h: h[0])      # (the first of equal values)
+            seq, rows = ([int(self.eos)], []) if kind == "eos" else ([], [])
+            for t in range(s - len(seq), -1, -1):              # from the last picked token back to the first, through the parents
+                seq.append(tokens[t][n * B + slot])
+                rows.append(t * R + n * B + slot)
+                slot = parents[t][n * B + slot]
+            winners.append((seq[::-1], value, rows[::-1][:len(seq) - 1]))
+        return winners
 
 
 class DecodeState:
@@ -310,9 +520,9 @@ class GenerateMixin:
             st.graph = g                                        # capture records, it does not execute: fall through to the replay
         st.graph.replay()
 
-    def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, weight_bits, fused, key):
-        """(weight_bits: the call's weight mode -- None, 8, or "mxfp4" for weight_format.)  What every generate() route does before its loop: the prompts (input_ids [N, L], trimmed; attention_mask = the ragged call's mask, else None) through
-        the prefill, K and V of prompt n into physical row n * rows of the decode state of N * rows rows (rows = 1, or the beams per prompt), the state made ready
+    def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, mode, fused, key):
+        """What every generate() route does before its loop: the prompts (input_ids [N, L], trimmed; attention_mask = the ragged call's mask, else None) through the prefill
+        in the call's weight mode (`_weight_mode`), K and V of prompt n into physical row n * rows of the decode state of N * rows rows (rows = 1, or the beams per prompt), the state made ready
         for the call's route.  The states are kept per (N * rows, capacity) + key.  -> (state, final-norm hidden [N, T, H], T, embedding weights, lm_head weights)."""
         self.prepare()
         c = self.config
@@ -339,16 +549,16 @@ class GenerateMixin:
         def keep_kv(i, qkv):                                   # qkv [N*T, 3H] after the in-place RoPE of q and k
             st.k[i, ::rows, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
             st.v[i, ::rows, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
-        if weight_bits is None:
+        if mode is None:
             st.qw = None
             hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
         else:
-            st.qw = self._quantize_decode_weights(weight_bits)
+            st.qw = self._quantize_decode_weights(mode)
             hidden_p = self._prefill_quantised(embeds, plan.key_mask, st.qw, keep_kv)
         ragged = attention_mask is not None or rows > 1       # beams: every row at its own device-side position (they are equal; the per-row kernels read them)
-        if fused != st.fused or weight_bits != st.bits or ragged != st.ragged:
-            st.fused, st.bits, st.ragged, st.graph, st.warm = fused, weight_bits, ragged, None, False      # a different kernel sequence: capture again
-        st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0 and weight_bits is None) else None
+        if fused != st.fused or mode != st.bits or ragged != st.ragged:
+            st.fused, st.bits, st.ragged, st.graph, st.warm = fused, mode, ragged, None, False      # a different kernel sequence: capture again
+        st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0 and mode is None) else None
         return st, hidden_p, T, emb_w, self._w("lm_head.weight", F)
 
     @torch.no_grad()
@@ -416,173 +626,56 @@ class GenerateMixin:
         route is launch for launch the one above.  Measured at Llama-7B (profiles/generation_controls.md): the four controls add 0.007 / -0.001 ms per token at 1 / 8
         sequences (inside the run-to-run spread) where Hugging Face's processor objects on the device add 0.104 / 0.122.  Out of scope (ValueError): any of the four with
         num_beams >= 2 -- HF applies processors to the log-softmax there, not to the logits: another rule and another `beam_step`."""
-        controls = not (repetition_penalty == 1.0 and no_repeat_ngram_size == 0 and min_new_tokens == 0 and suppress_tokens is None)
-        if controls:                                           # any of the four off its default: the logits-processor launch before every pick
-            if isinstance(repetition_penalty, bool) or not (isinstance(repetition_penalty, (int, float)) and math.isfinite(repetition_penalty) and repetition_penalty > 0):
-                raise ValueError(f"repetition_penalty must be a finite number > 0 (1 = off), got {repetition_penalty!r}")
-            for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
-                if not (isinstance(v, int) and not isinstance(v, bool) and 0 <= v < 2 ** 31):
-                    raise ValueError(f"{name} must be an integer >= 0 (0 = off), got {v!r}")
-            if min_new_tokens > 0 and eos_token_id is None:
-                raise ValueError("min_new_tokens needs an eos_token_id: it bans that token until enough tokens were emitted")
-            if min_new_tokens > max_new_tokens:
-                raise ValueError(f"min_new_tokens = {min_new_tokens} exceeds max_new_tokens = {max_new_tokens}")
-            if suppress_tokens is not None:
-                vocab = self.config.llama.vocab
-                try:
-                    suppress_tokens = list(suppress_tokens)
-                except TypeError:
-                    raise ValueError(f"suppress_tokens must be a sequence of integers in [0, {vocab}), got {suppress_tokens!r}") from None
-                if not suppress_tokens or not all(isinstance(t, int) and not isinstance(t, bool) and 0 <= t < vocab for t in suppress_tokens):
-                    raise ValueError(f"suppress_tokens must be a non-empty sequence of integers in [0, vocab = {vocab}), got {suppress_tokens!r}")
-            if isinstance(num_beams, int) and num_beams >= 2:
-                raise ValueError("repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens with num_beams >= 2 are out of scope: beam search applies "
-                                 "processors to the log-softmax, another rule")
-        if not (isinstance(num_beams, int) and not isinstance(num_beams, bool) and num_beams >= 1):
-            raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
-        if beam_cache not in ("indirect", "copy"):
-            raise ValueError(f"beam_cache must be 'indirect' or 'copy', got {beam_cache!r}")
-        if not isinstance(early_stopping, bool):
-            raise ValueError(f"early_stopping must be True or False ('never' is out of scope), got {early_stopping!r}")
-        if isinstance(length_penalty, bool) or not (isinstance(length_penalty, (int, float)) and math.isfinite(length_penalty)):
-            raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
-        if num_beams == 1 and not (length_penalty == 1.0 and early_stopping is False and not return_beam_scores and beam_cache == "indirect" and _beam_trace is None):
-            raise ValueError("length_penalty, early_stopping, return_beam_scores and beam_cache need num_beams >= 2")
-        if num_beams >= 2:
-            if do_sample:
-                raise ValueError("do_sample with num_beams >= 2 (beam sampling) is out of scope")
-            if not fuse_decode:
-                raise ValueError("num_beams >= 2 needs fuse_decode=True (the beam-indexed cache is built into the fused decode step only)")
-            if self.config.llama.head_dim != 128:
-                raise ValueError(f"num_beams >= 2 needs head_dim 128, got {self.config.llama.head_dim}: the two-launch route is out of scope")
-            if num_beams > 16 or 2 * num_beams > self.config.llama.vocab:
-                raise ValueError(f"num_beams must be <= 16 and 2 * num_beams <= vocab = {self.config.llama.vocab}, got {num_beams}")
-        defaults = temperature == 1.0 and top_k == 0 and top_p == 1.0 and seed is None and uniforms is None and not return_logprobs
-        if not do_sample and not defaults:
-            raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True (greedy decoding takes none of them)")
-        if do_sample:
-            if not (isinstance(temperature, (int, float)) and math.isfinite(temperature) and temperature > 0):
-                raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
-            if not (isinstance(top_k, int) and not isinstance(top_k, bool) and 0 <= top_k < 2 ** 31):
-                raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k!r}")
-            if not (isinstance(top_p, (int, float)) and 0 < top_p <= 1):
-                raise ValueError(f"top_p must be in (0, 1] (1 = off), got {top_p!r}")
-            if seed is not None and uniforms is not None:
-                raise ValueError("pass seed= or uniforms=, not both")
-            if uniforms is not None and (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or
-                                         tuple(uniforms.shape) != (input_ids.shape[0], max_new_tokens)):
-                raise ValueError(f"uniforms must be an fp32 tensor [N, max_new_tokens] = {(input_ids.shape[0], max_new_tokens)}, got "
-                                 f"{getattr(uniforms, 'dtype', type(uniforms))} {tuple(getattr(uniforms, 'shape', ()))}")
+        controls = _check_controls(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens, num_beams)
+        _check_beams(self, num_beams, length_penalty, early_stopping, return_beam_scores, beam_cache, _beam_trace, do_sample, fuse_decode)
+        sampling = _check_sampling(do_sample, temperature, top_k, top_p, seed, uniforms, return_logprobs, input_ids, max_new_tokens)
         mode = _weight_mode(weight_bits, weight_format, fuse_decode)
+        fill = 0 if pad_token_id is None else int(pad_token_id)      # what finished rows and the padding hold
         if num_beams >= 2:
-            if not defaults:
-                raise ValueError("temperature, top_k, top_p, seed, uniforms and return_logprobs need do_sample=True")
-            return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, mode, attention_mask, num_beams,
-                                        float(length_penalty), early_stopping, return_beam_scores, beam_cache, _beam_trace)
-        lens = None                                            # prompt lengths L_i on the host, ragged calls only
-        if attention_mask is not None:
-            input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
-        if lens is not None:
-            if not fuse_decode:
-                raise ValueError("prompts of different lengths need fuse_decode=True (the per-row positions are built into the fused decode step only)")
-            if self.config.llama.head_dim != 128:
-                raise ValueError(f"prompts of different lengths need head_dim 128, got {self.config.llama.head_dim}: per-row key counts for the two-launch "
-                                 "route (llmseg_rope_kv_append + llmseg_attn_fwd) are out of scope")
-            fill = 0 if pad_token_id is None else int(pad_token_id)
-            input_ids = torch.where(attention_mask.to(input_ids.device), input_ids, torch.full_like(input_ids, fill))
-        ragged = lens is not None
-        if controls and input_ids.shape[1] + max_new_tokens > ops.LOGITS_HIST_CAP:
-            raise ValueError(f"repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens keep a history of prompt + max_new_tokens = "
-                             f"{input_ids.shape[1]} + {max_new_tokens} ids per row: more than the cap of {ops.LOGITS_HIST_CAP}")
-        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, mode, bool(fuse_decode), ())
-        dev = self.device_
-        N, L = input_ids.shape
-        Pn, H = self.config.n_img_tokens, self.config.llama.hidden
-        if ragged:
-            t_rows = (lens - 1 + Pn).to(dev)                    # T_i: row i's prefill length = the position of its first fed token
-            st.pos_rows.copy_(t_rows.to(torch.int32))
-            hidden = torch.zeros((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
-            own = torch.arange(T, device=dev)[None, :] < t_rows[:, None]
-            hidden[:, :T] = torch.where(own[:, :, None], hidden_p, torch.zeros_like(hidden_p))
-            last = torch.arange(N, device=dev) * T + t_rows - 1                            # each row's own last prompt position
-            logits = ops.gemm(ops.gather_rows(hidden_p.reshape(N * T, H), last), lm_w)
-            slot = torch.arange(N, device=dev) * hidden.shape[1] + t_rows - 1                # flat row of `hidden` that holds each sequence's newest state
-        else:
-            st.pos.copy_(torch.tensor([T, T + 1], dtype=torch.int32))
-            hidden = torch.empty((N, T + max_new_tokens - 1, H), device=dev, dtype=BF16)
-            hidden[:, :T] = hidden_p
-            logits = ops.gemm(hidden_p[:, -1].contiguous(), lm_w)     # only the last position's logits are needed
-        seqs = [input_ids.to(dev)]
-        unfinished = torch.ones((N,), dtype=torch.int64, device=dev)
-        n_new = 0
-        if do_sample:
-            if uniforms is None:
-                gen = None if seed is None else torch.Generator(device=dev).manual_seed(int(seed))
-                uniforms = torch.rand((N, max_new_tokens), device=dev, dtype=torch.float32, generator=gen)
-            u_steps = uniforms.to(dev).t().contiguous()        # [max_new_tokens, N]: step s reads one contiguous row
-            lps = []
-        if controls:                                           # each row's history at a fixed address: its own prompt, left-aligned; the launch below appends to it
-            hist = torch.zeros((N, L + max_new_tokens), dtype=torch.int64, device=dev)
-            hist[:, :L] = seqs[0]
-            hist_len = (lens.to(torch.int32) if ragged else torch.full((N,), L, dtype=torch.int32)).to(dev)
-            suppress = None if suppress_tokens is None else torch.tensor(suppress_tokens, dtype=torch.int32, device=dev)
-            nxt = None
+            return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, fill, use_graph, mode, attention_mask, num_beams, float(length_penalty),
+                                        early_stopping, return_beam_scores, beam_cache, _beam_trace)
+        input_ids, attention_mask, lens = _row_prompts(self, input_ids, attention_mask, fuse_decode, fill, controls, max_new_tokens)
+        return self._generate_rows(images_clip, input_ids, attention_mask, lens, max_new_tokens, eos_token_id, pad_token_id, fill, use_graph, bool(fuse_decode), mode,
+                                   sampling, controls)
+
+    def _generate_rows(self, images_clip, input_ids, attention_mask, lens, max_new_tokens, eos_token_id, pad_token_id, fill, use_graph, fused, mode, sampling, controls):
+        """`generate(num_beams=1)`: the arguments are checked there.  One token per row and step: the pick (`_make_pick`: arg-max or sampling, after the controls),
+        the stop test, the decode step on the picked tokens; where positions, hidden states and sequences go is the layout's (uniform, or ragged: lens is not None)."""
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, mode, fused, ())
+        layout = _uniform_rows(st, hidden_p, lm_w, max_new_tokens) if lens is None else _ragged_rows(st, hidden_p, lm_w, max_new_tokens, lens, self.config.n_img_tokens, fill)
+        logits, store, pack = layout
+        seqs, n_new = [input_ids.to(self.device_)], 0
+        pick, live = _make_pick(seqs[0], lens, max_new_tokens, eos_token_id, pad_token_id, sampling, controls)
         while True:
-            if controls:                                       # one launch: the token just picked joins the history, then the processors rewrite the step's logits in place
-                logits = ops.logits_process(logits, hist, hist_len, append=nxt, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                                            ban_token=eos_token_id if n_new < min_new_tokens else None, suppress=suppress)
-            if do_sample:                                      # one launch: the pick, pad for finished rows and the update of `unfinished`
-                nxt, lp, _, _ = ops.sample_tokens(logits, temperature, top_k, top_p, u_steps[n_new], eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                                  unfinished=unfinished, want_logprob=return_logprobs)
-                if return_logprobs:
-                    lps.append(lp[:, None])
-            else:
-                nxt = logits.float().argmax(-1)
-                if eos_token_id is not None:
-                    nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
+            nxt = pick(logits, n_new)
             seqs.append(nxt[:, None])
             n_new += 1
-            if eos_token_id is not None:
-                if not do_sample:
-                    unfinished = unfinished * (nxt != eos_token_id).long()
-                if int(unfinished.max()) == 0:                 # the one host synchronisation of a step (HF's loop has the same)
-                    break
-            if n_new == max_new_tokens:
+            # all rows finished (the one host synchronisation of a step; HF's loop has the same), or max_new_tokens tokens added
+            if (eos_token_id is not None and int(live.unfinished.max()) == 0) or n_new == max_new_tokens:
                 break
             st.x.copy_(ops.gather_rows(emb_w, nxt))
             self._decode_step(st, use_graph)
-            if ragged:
-                hidden.view(-1, H).index_copy_(0, slot.add_(1), st.hidden)
-            else:
-                hidden[:, T + n_new - 1] = st.hidden
+            store(st.hidden, n_new)
             logits = st.logits
-        if ragged:                                             # row i: prompt, new tokens, fill
-            out = torch.cat([seqs[0], torch.full((N, n_new), fill, dtype=torch.int64, device=dev)], 1)
-            out.scatter_(1, lens.to(dev)[:, None] + torch.arange(n_new, device=dev)[None, :], torch.cat(seqs[1:], 1))
-            res = (out, hidden[:, :T + n_new - 1])
-        else:
-            res = (torch.cat(seqs, 1), hidden[:, :T + n_new - 1])
-        return res + (torch.cat(lps, 1),) if return_logprobs else res
+        res = pack(seqs, n_new)
+        return res + (torch.cat([lp[:, None] for lp in live.logprobs], 1),) if sampling is not None and sampling["return_logprobs"] else res
 
-    def _generate_beams(self, images_clip, input_ids, max_new_tokens, eos_token_id, pad_token_id, use_graph, weight_bits, attention_mask, B, length_penalty,
-                        early_stopping, return_beam_scores, beam_cache, trace):
-        """`generate(num_beams=B >= 2)`: the arguments are checked there."""
+    def _generate_beams(self, images_clip, input_ids, max_new_tokens, eos_token_id, fill, use_graph, mode, attention_mask, B, length_penalty, early_stopping,
+                        return_beam_scores, beam_cache, trace):
+        """`generate(num_beams=B >= 2)`: the arguments are checked there.  The device loop; hypotheses, the done rule and the winners are the `BeamBook`'s."""
         if attention_mask is not None:
             input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
             if lens is not None:
                 raise ValueError("num_beams >= 2 with prompts of different lengths (an attention_mask that is ragged after trimming) is out of scope")
         indirect = beam_cache == "indirect"
         # a state of its own: a greedy call on N * B sequences never meets a beam call's graph
-        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, None, B, max_new_tokens, weight_bits, True, ("beams", beam_cache))
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, None, B, max_new_tokens, mode, True, ("beams", beam_cache))
         dev = self.device_
         N, L = input_ids.shape
         R, H = N * B, self.config.llama.hidden
-        fill = 0 if pad_token_id is None else int(pad_token_id)
         if st.src_a is None:                                   # a new state
-            st.src_a = torch.zeros((R, st.cap), device=dev, dtype=torch.int32)
-            st.src_b = torch.zeros((R, st.cap), device=dev, dtype=torch.int32)
-            if indirect:
-                st.beam_src = st.src_a
+            st.src_a, st.src_b = (torch.zeros((R, st.cap), device=dev, dtype=torch.int32) for _ in range(2))
+            st.beam_src = st.src_a if indirect else None
         st.pos_rows.fill_(T)
         logits = ops.gemm(hidden_p[:, -1].contiguous(), lm_w)      # [N, V]: the first pick reads one row per prompt
         scores = torch.zeros((N,), device=dev, dtype=torch.float32)
@@ -591,8 +684,7 @@ class GenerateMixin:
         rec = torch.zeros((2 * N + 2 * N * B,), device=dev, dtype=torch.int32)
         ws = torch.empty((R * 2 * B,), device=dev, dtype=torch.int64)
         row0 = torch.arange(R, device=dev) // B * B
-        done = [False] * N
-        pools = [[] for _ in range(N)]                         # per prompt: (value, kind, step, slot), the B best by value
+        book = BeamBook(N, B, length_penalty, early_stopping, eos_token_id)
         toks, pars, hids = [], [], []
         step = 0
         while True:
@@ -603,24 +695,16 @@ class GenerateMixin:
             st.src_a.copy_(st.src_b)                           # (entries at or beyond a row's position are never read: whatever they hold is copied along)
             rec_h = rec.cpu()                                  # the one host synchronisation of a step
             if trace is not None:
-                trace.append(dict(logits=logits.float().cpu(), scores=scores.cpu(), done=list(done), next_token=out["next_token"].cpu(), parent=out["parent"].cpu(),
+                trace.append(dict(logits=logits.float().cpu(), scores=scores.cpu(), done=list(book.done), next_token=out["next_token"].cpu(), parent=out["parent"].cpu(),
                                   next_scores=out["next_scores"].cpu(), rec=rec_h.clone()))
             toks.append(out["next_token"])
             pars.append(out["parent"])
-            sb, fc = rec_h[:N].view(torch.float32).tolist(), rec_h[N:2 * N].tolist()
-            fp, fs = rec_h[2 * N:2 * N + N * B].view(N, B).tolist(), rec_h[2 * N + N * B:].view(torch.float32).view(N, B).tolist()
-            g = step + 1
-            for n in range(N):
-                if done[n]:
-                    continue
-                for k in range(fc[n]):
-                    self._beam_pool_add(pools[n], B, (fs[n][k] / g ** length_penalty, "eos", step, fp[n][k]))
-                if len(pools[n]) >= B and (early_stopping or min(h[0] for h in pools[n]) >= sb[n] / g ** length_penalty):
-                    done[n] = True
+            book.step(step, rec_h[:N].view(torch.float32).tolist(), rec_h[N:2 * N].tolist(), rec_h[2 * N:2 * N + N * B].view(N, B).tolist(),
+                      rec_h[2 * N + N * B:].view(torch.float32).view(N, B).tolist())
             step += 1
-            if all(done) or step == max_new_tokens:
+            if all(book.done) or step == max_new_tokens:
                 break
-            done_dev.copy_(torch.tensor(done, dtype=torch.int32))
+            done_dev.copy_(torch.tensor(book.done, dtype=torch.int32))
             scores = out["next_scores"]
             if not indirect:                                   # the yardstick: move every layer's K and V to the beams' new rows
                 gidx = row0 + out["parent"]
@@ -630,37 +714,9 @@ class GenerateMixin:
             self._decode_step(st, use_graph)
             hids.append(st.hidden.clone())
             logits = st.logits
-        last = out["next_scores"].cpu().tolist()
-        for n in range(N):                                     # a prompt that is not done: its live beams are hypotheses of `step` tokens
-            if not done[n]:
-                for i in range(B):
-                    self._beam_pool_add(pools[n], B, (last[n * B + i] / step ** length_penalty, "live", step - 1, i))
-        tok_h, par_h = torch.stack(toks).cpu().tolist(), torch.stack(pars).cpu().tolist()      # [steps, R]
-        rows, gather, values = [], [], []
-        for n in range(N):
-            best = pools[n][0]
-            for h in pools[n][1:]:
-                if h[0] > best[0]:
-                    best = h
-            value, kind, s, slot = best
-            seq, slots = [], [None] * (s + 1)
-            if kind == "eos":
-                seq.append(int(eos_token_id))
-                s -= 1
-            while s >= 0:
-                slots[s] = slot
-                seq.append(tok_h[s][n * B + slot])
-                slot = par_h[s][n * B + slot]
-                s -= 1
-            seq.reverse()
-            rows.append(seq)
-            values.append(value)
-            gather.append([t * R + n * B + slots[t] for t in range(len(seq) - 1)])      # the state of each fed token: every token but the last
+        rows, values, gather = zip(*book.finish(out["next_scores"].cpu().tolist(), torch.stack(toks).cpu().tolist(), torch.stack(pars).cpu().tolist()))
         n_new = max(len(r) for r in rows)
-        out_ids = torch.full((N, L + n_new), fill, dtype=torch.int64)
-        out_ids[:, :L] = input_ids.cpu()
-        for n, r in enumerate(rows):
-            out_ids[n, L:L + len(r)] = torch.tensor(r, dtype=torch.int64)
+        out_ids = torch.cat([input_ids.cpu(), torch.tensor([r + [fill] * (n_new - len(r)) for r in rows], dtype=torch.int64)], 1)      # row i: prompt, the winner, fill
         hidden = torch.zeros((N, T + n_new - 1, H), device=dev, dtype=BF16)
         hidden[:, :T] = hidden_p
         if hids:
@@ -671,14 +727,7 @@ class GenerateMixin:
         res = (out_ids.to(dev), hidden)
         return res + (torch.tensor(values, dtype=torch.float32, device=dev),) if return_beam_scores else res
 
-    @staticmethod
-    def _beam_pool_add(pool, B, hyp):
-        """Hugging Face's BeamHypotheses.add: keep the B best by value; a newcomer enters a full pool only when it beats the worst, which then leaves."""
-        if len(pool) < B:
-            pool.append(hyp)
-        elif hyp[0] > min(h[0] for h in pool):
-            worst = min(range(len(pool)), key=lambda i: pool[i][0])
-            pool[worst] = hyp
+    _beam_pool_add = staticmethod(BeamBook.add)
 
     @staticmethod
     def _ragged_prompts(input_ids, attention_mask):

@@ -1,9 +1,10 @@
 """CPU: beam search -- the rule of tests/beam_checks.py against the installed transformers (`LlamaForCausalLM.generate(num_beams=...)` on a tiny random fp32
 model built from a config); the case table of llmseg_beam_step meets its conditions (every gap among the 2 B + 1 best fp64 scores >= 16 x the bound, exact ties
 only where planted, eos at the rank its case names); the fp32 / integer emulation of the kernel's arithmetic stays under the bound on every case with exact
-picks; every named mutant fails a check; the header, the binding and INTEGRATION.md agree on the two symbols and bad arguments are refused before any launch."""
+picks; every named mutant fails a check; generate()'s host bookkeeping (`BeamBook`) driven by the rule's own picks returns the rule's winners; the header, the binding and INTEGRATION.md agree on the two symbols and bad arguments are refused before any launch."""
 import ctypes as C
 import functools
+import math
 import os
 import re
 
@@ -238,6 +239,70 @@ def test_decode_attn_beams_refuses_bad_arguments_before_any_launch():
                                           a["ld_src"], a["capacity"], a["N"], a["heads"], a["head_dim"], 0.1, p(a["out"]), a["ldo"], None, 0, None)
         assert rc == -1 and b"decode_attn_beams" in lib.llmseg_last_error(), bad
     assert lib.llmseg_launch_count() == n0
+
+
+# ------------------------------------------------------------------------------------------------------ generate()'s host bookkeeping: BeamBook
+BOOK_MAX_NEW, BOOK_V, BOOK_PAD = 4, 8, 7
+BOOK_SETTINGS = [(B, eos, lp, early) for B in (2, 3) for eos in (1, None) for lp in (0.5, 1.0, 2.0) for early in (False, True)]
+
+
+def _book_logits(n):
+    """prompt n's logits, a fixed function of its generated tokens: V = 8, eos = 1 likely enough to finish hypotheses, prompt 0 much more so than prompt 1"""
+    def logits_fn(seqs):
+        rows = []
+        for s in seqs:
+            l = torch.randn(BOOK_V, generator=torch.Generator().manual_seed(1000 * n + sum((i + 1) * (t + 1) * 31 ** i for i, t in enumerate(s)))).double() * 1.5
+            l[1] += (1.0 + 2.0 * len(s)) * (1 - n) - 1.0 * n
+            rows.append(l)
+        return torch.stack(rows)
+    return logits_fn
+
+
+@pytest.mark.parametrize("setting", BOOK_SETTINGS, ids=[f"B{s[0]}_eos{s[1]}_lp{s[2]}_early{s[3]}" for s in BOOK_SETTINGS])
+def test_beam_book_keeps_the_rules_pools_and_backtraces_the_winner(setting):
+    """generate()'s loop without a device: per pick the records `llmseg_beam_step` would write, made by `walk` on hand-built logits (a done prompt's rows emit pad from
+    their own slots, as the kernel's do), go through `BeamBook.step`; `BeamBook.finish` must return, for both prompts, the winner of `beam_checks.search`."""
+    from llmseg_amd.generate import BeamBook
+    B, eos, lp, early = setting
+    N = 2
+    want = [bc.search(_book_logits(n), B, eos, BOOK_MAX_NEW, lp, early) for n in range(N)]
+    for n, (p, _) in enumerate(want):                          # the reference side: no two hypotheses a pool ever met have the same value (else the winner is not unique)
+        vals = [s / (g + 1) ** lp for g, pick in enumerate(p.picks) for _, s in pick["fin"]] + ([] if p.done else [s / p.steps ** lp for s in p.scores])
+        assert len(set(vals)) == len(vals), f"prompt {n}: equal values among the hypotheses {vals}"
+    book = BeamBook(N, B, float(lp), early, eos)
+    seqs, scores = [[[]] for _ in range(N)], [[0.0] for _ in range(N)]
+    tokens, parents, step, done_after = [], [], 0, [None] * N
+    while True:
+        rec = dict(step_best=[0.0] * N, fin_count=[0] * N, fin_parent=[[-7] * B for _ in range(N)], fin_score=[[math.nan] * B for _ in range(N)])
+        tok, par = [], []
+        for n in range(N):
+            if book.done[n]:
+                tok, par = tok + [BOOK_PAD] * B, par + list(range(B))          # (its scores stay as they are)
+                continue
+            lg = _book_logits(n)(seqs[n])
+            pick = bc.walk(torch.tensor(scores[n], dtype=torch.float64)[:, None] + lg - torch.logsumexp(lg, -1, keepdim=True), B, eos)
+            rec["step_best"][n], rec["fin_count"][n] = pick["best"], len(pick["fin"])
+            for k, (b, s) in enumerate(pick["fin"]):
+                rec["fin_parent"][n][k], rec["fin_score"][n][k] = b, s
+            seqs[n], scores[n] = [seqs[n][b] + [v] for b, v in zip(pick["parents"], pick["tokens"])], pick["scores"]
+            tok, par = tok + pick["tokens"], par + pick["parents"]
+        tokens.append(tok)
+        parents.append(par)
+        book.step(step, **rec)
+        step += 1
+        done_after = [step if d and a is None else a for d, a in zip(book.done, done_after)]
+        if all(book.done) or step == BOOK_MAX_NEW:
+            break
+    winners = book.finish([s for n in range(N) for s in scores[n]], tokens, parents)
+    print(f"\n{setting}: {step} picks, the prompts end after {[p.steps for p, _ in want]}, done {book.done}, winners {[(w[0], round(w[1], 4)) for w in winners]}")
+    assert done_after == [p.steps if p.done else None for p, _ in want] and step == max(p.steps for p, _ in want), "a prompt is done at another pick than the rule's"
+    for n, ((p, (value, toks)), (seq, val, gather)) in enumerate(zip(want, winners)):
+        assert seq == toks, f"prompt {n}: tokens {seq}, the rule's {toks}"
+        assert abs(val - value) <= 1e-4, f"prompt {n}: value {val!r}, the rule's {value!r}"
+        # the hidden state of every fed token: pick t's row of the beam that carries the winner there, i.e. whose tokens so far are the winner's first t + 1
+        assert all(n * B <= g - t * N * B < (n + 1) * B for t, g in enumerate(gather)) and [tokens[t][g - t * N * B] for t, g in enumerate(gather)] == seq[:-1]
+    if eos is not None and (early or B == 2):                  # (three beams: the pool's worst outranks the best candidate only at the last pick)
+        assert want[0][0].steps < want[1][0].steps, "the case must finish one prompt before the other"
 
 
 def test_generate_signature_and_defaults():
