@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args, 5 = llmseg_lora_down_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (20: llmseg_logits_process; 19: llmseg_quantize_rows_mxfp4, llmseg_gemm_mxfp4 and llmseg_gemm_mxfp4_args; 18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (21: llmseg_kv_quantize_mxfp8, llmseg_decode_attn_mxfp8; 20: llmseg_logits_process; 19: llmseg_quantize_rows_mxfp4, llmseg_gemm_mxfp4 and llmseg_gemm_mxfp4_args; 18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 20
+#define LLMSEG_ABI_VERSION 21
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -420,6 +420,48 @@ int llmseg_decode_attn_rows(const void* qkv, int64_t ld, const float* cos, const
 int llmseg_decode_attn_beams(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                              const int32_t* pos_rows_dev, const int32_t* src, int64_t ld_src, int64_t capacity, int64_t N, int32_t heads, int32_t head_dim,
                              float scale, void* out, int64_t ldo, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ---- MXFP8 KV cache (OCP Microscaling: 8-bit E4M3 elements -- the OCP `fn` encoding gfx950 has natively, not MI300's `fnuz` -- and one E8M0 scale
+ * per block of 32) ----
+ * 8.25 bits per cached value: 4224 bytes instead of 8192 per token, layer and tensor at Llama-7B.  The rule, per bf16 row of D elements (D % 32 == 0, finite
+ * values) and per block of 32 consecutive elements:
+ *   amax = the largest |x| of the block;
+ *   e = the smallest integer >= -127 with amax <= 448 * 2^e (amax == 0: e = -127); the scale byte is e + 127, one E8M0 byte.  For a normal
+ *     amax = m * 2^E, m in [1, 2): e = E - 8 when m <= 1.75, else E - 7 (integer work on the bf16 bits).  A finite bf16 never needs e > 120: nothing
+ *     saturates, and the NaN code 0x7f is never produced;
+ *   y = x / 2^e (exact, |y| <= 448) is rounded to the nearest OCP E4M3 value (sign, 4 exponent bits of bias 7, 3 mantissa bits), ties to the even
+ *     code, subnormals included: the smallest non-zero magnitude is 2^-9, and 2^-10 rounds to 0.  The sign bit is cleared when the magnitude is 0
+ *     (-0 is never stored);
+ *   x_hat = bf16(element * 2^e) has four significant bits: exact whenever it is a normal bf16.  A result below the smallest normal bf16 (possible only
+ *     under a scale byte <= 9) is flushed to +0, in x_hat and in the decode step alike.  (|x| >= 1.96875 * 2^127 rounds to y = 256 under e = 120: element * 2^e
+ *     is 2^128 there, not a finite bf16.)  x_hat is a fixed point of the rule in value; its bytes are too unless amax was rounded down onto 1.75 * 2^E (y = 224
+ *     under e = E - 7), which the rule then stores as y = 448 under e = E - 8.
+ * Layout of a cache row [n][t] of heads * 128 elements: bytes q[n][t][h * 128 + d], scales scale[n][t][h * 4 + d / 32].
+ *
+ * llmseg_kv_quantize_mxfp8: ONE launch over batch x rows rows of D elements.  Row (b, r) of an operand lives at base + b * stride_b + (row0 + r) * stride_r
+ * (strides in elements of the operand: bf16 for x and x_hat, bytes for q and scale), row0 = row0_dev[b * row0_stride] (int32 in device memory,
+ * row0_stride 0 or 1) or 0 when row0_dev is NULL: the same first row for every operand.  Outputs: q + scale (nullable as a pair) and x_hat bf16 (nullable);
+ * at least one must be given.  x_hat may alias x (same strides): a block is read whole before any of it is written.  Two uses: the prefill (K and V
+ * slices of the packed q|k|v buffer -> cache rows [n][0 .. T)), and a bf16 cache that holds x_hat, rewritten in place at slot [n][pos_n] with
+ * row0_dev = the decode step's position tensor.  Checked before the launch: x non-NULL; x and x_hat 16-byte aligned with strides % 8 == 0, q 8-byte
+ * aligned with strides % 8 == 0, row0_dev 4-byte aligned; D % 32 == 0; batch, rows >= 1; every row stride >= the row's extent (D, or D / 32 for scale) and,
+ * for batch > 1, every batch stride >= rows * row stride. */
+int llmseg_kv_quantize_mxfp8(const void* x, int64_t x_stride_b, int64_t x_stride_r, void* q, int64_t q_stride_b, int64_t q_stride_r, void* scale,
+                             int64_t s_stride_b, int64_t s_stride_r, void* x_hat, int64_t h_stride_b, int64_t h_stride_r, const int32_t* row0_dev,
+                             int64_t row0_stride, int64_t batch, int64_t rows, int64_t D, void* stream);
+/* llmseg_decode_attn / _rows / _beams on the packed cache: kcache / vcache uint8 [N][capacity][heads * 128] (cache_stride_n bytes per sequence), kscale /
+ * vscale uint8 [N][capacity][heads * 4] (scale_stride_n bytes per sequence).  pos_stride 0: one position *pos_dev for every sequence; 1: pos_dev[n].  src
+ * (nullable): the beam table of llmseg_decode_attn_beams with ld_src >= capacity > 0; NULL: every row reads its own row.  The rule of a step: the new
+ * token's k (after RoPE) and v take part in this step's attention as the bf16 values just computed, exactly as on the bf16 routes; slot [n][pos] receives
+ * their MXFP8 rounding (128 bytes and four scale bytes per head and tensor); every earlier key is element * 2^e, decoded on load.  One more compile-time
+ * instance of the one kernel: key -> lane mapping, trip, split count, scratch and merge are the bf16 routes', so `out` equals, bit for bit, the bf16 entry
+ * point on the cache of x_hat values.  Bytes beyond a row's position are never read.  Checked before the launch: what the bf16 entry points check with
+ * 8-byte instead of 16-byte cache alignment, cache_stride_n >= heads * 128, the scales non-NULL and 4-byte aligned with scale_stride_n % 4 == 0 and >= heads * 4,
+ * pos_stride 0 or 1, head_dim 128. */
+int llmseg_decode_attn_mxfp8(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                             void* kscale, void* vscale, int64_t scale_stride_n, const int32_t* pos_dev, int64_t pos_stride, const int32_t* src /* nullable */,
+                             int64_t ld_src, int64_t capacity, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
+                             void* scratch, int64_t scratch_bytes, void* stream);
 
 /* y[i] = act(x[i]), bf16, n % 8 == 0, in place allowed (the GELU between LayerNorm2d and the second transposed convolution of SAM's
  * mask decoder, mask_decoder.py:53-63: every other activation on the path rides in a GEMM epilogue) */

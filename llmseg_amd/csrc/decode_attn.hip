@@ -5,8 +5,10 @@
 // online softmax over its keys with all of a trip's K and V rows requested together (one HBM round trip per 64 keys per workgroup).
 // The three entry points -- one position for every sequence, one position per sequence, and one position per sequence over a beam-indexed
 // cache -- are one launch function over one kernel: RoPE, the append to [n][pos], the split count, the 16-lane key groups, the trip of 64
-// keys, the online softmax and the merge exist once.
+// keys, the online softmax and the merge exist once.  A fourth entry point runs the same step on an MXFP8 cache (E4M3 bytes + one E8M0 scale byte per 32
+// dims, mxfp8.h): one more compile-time instance of the kernel, in which only the append, the load and the unpack differ.
 #include "common.h"
+#include "mxfp8.h"
 #include <algorithm>
 
 namespace {
@@ -23,13 +25,38 @@ struct DecP {
   // TABLE only: key t < pos of row n is read from the physical cache row src[n * ld_src + t].  (Last, so that the plain instance finds every argument it reads
   // where it always was.)
   const int32_t* src; long ld_src;
+  // MX8 only: kc / vc are E4M3 bytes [n][t][heads * 128] (cstride in bytes), ksc / vsc their scale bytes [n][t][heads * 4] (sstride per sequence)
+  uint8_t *ksc, *vsc; long sstride;
 };
+
+// Eight E4M3 bytes under scale byte sb -> the eight fp32 values element * 2^e.  From scale byte 10 on every non-zero result is a normal number (2^-9 * 2^-117 =
+// 2^-126), so the hardware's packed E4M3 -> fp32 conversion (OCP encoding on gfx950, exact) and an exact ldexp give the value whatever the denormal mode; below
+// that the integer decode of mxfp8.h, which flushes what is not a normal bf16 to +0.  Both equal the bf16 x_hat the quantiser writes.  (The code 0x80, -0, is
+// never stored by the quantiser or the append.)
+typedef float mx8_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void mx8_unpack8(uint32_t lo, uint32_t hi, int sb, float* f) {
+  if (sb >= 10) {
+    const int e = sb - 127;
+    const mx8_f2 a = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
+    const mx8_f2 c = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
+    f[0] = ldexpf(a.x, e); f[1] = ldexpf(a.y, e); f[2] = ldexpf(b.x, e); f[3] = ldexpf(b.y, e);
+    f[4] = ldexpf(c.x, e); f[5] = ldexpf(c.y, e); f[6] = ldexpf(d.x, e); f[7] = ldexpf(d.y, e);
+  } else {
+    uint32_t w[4];
+    mx8_decode8(lo, hi, sb, w);
+    unpack8(make_uint4(w[0], w[1], w[2], w[3]), f);
+  }
+}
 
 // TABLE (beam search over a cache that is never moved): a beam's history lives wherever its ancestors wrote it, and re-ordering the beams
 // re-orders the int32 table (a few KB), not 32 layers of K and V.  The table entry of a key is uniform over the 16 lanes that own the key: one
 // 4-byte load per lane (the lanes of a group hit one address), issued ahead of the trip's K and V requests; no LDS stage.  A table that names
 // every row's own row gives the bits of the plain instance, which carries no trace of the table: the choice is made at compile time.
-template <bool TABLE>
+// MX8 (the packed cache): the new token's k and v take part in this step as the bf16 values in LDS, exactly as in the bf16 instances; slot [n][pos] receives
+// their MXFP8 rounding (lanes 0-15 of the owner's first wave encode k, lanes 16-31 v: four lanes per block of 32, as in the quantiser); every earlier key is
+// 8 bytes per lane + the key's scale word (the head's four scale bytes), unpacked to the fp32 values the x_hat cache would give (mx8_unpack8).  Lane mapping,
+// trip, split and merge are untouched, so the instance gives the bits of the bf16 instance on the cache of x_hat.
+template <bool TABLE, bool MX8>
 __global__ __launch_bounds__(256) void decode_attn_kernel(DecP p) {
   constexpr int HD = 128, UN = 4;
   __shared__ float qs[HD];
@@ -47,6 +74,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecP p) {
   bf16_t* vb = p.vc + (long)n * p.cstride + (long)h * HD;
   const bf16_t* kh = p.kc + (long)h * HD;                       // TABLE: physical row 0, the reads add src[n][j] * cstride
   const bf16_t* vh = p.vc + (long)h * HD;
+  const uint8_t *k8 = reinterpret_cast<const uint8_t*>(p.kc) + (long)h * HD, *v8 = reinterpret_cast<const uint8_t*>(p.vc) + (long)h * HD;      // MX8: physical row 0
+  const long SD = (long)p.heads * 4;                            // MX8: scale bytes per cache slot
   if (tid < 128) {
     const int i = tid & 63;
     if (tid < 64 || owner) {
@@ -57,21 +86,37 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecP p) {
       if (tid < 64) { qs[i] = bf2f(o1); qs[i + 64] = bf2f(o2); }
       else {
         knew[i] = o1; knew[i + 64] = o2;
-        kb[(long)pos * D + i] = o1; kb[(long)pos * D + i + 64] = o2;
+        if constexpr (!MX8) { kb[(long)pos * D + i] = o1; kb[(long)pos * D + i + 64] = o2; }
       }
     }
   } else if (tid < 192 && owner) {
     const int i = tid - 128;
     const bf16_t v1 = row[2 * D + i], v2 = row[2 * D + i + 64];
     vnew[i] = v1; vnew[i + 64] = v2;
-    vb[(long)pos * D + i] = v1; vb[(long)pos * D + i + 64] = v2;
+    if constexpr (!MX8) { vb[(long)pos * D + i] = v1; vb[(long)pos * D + i + 64] = v2; }
   }
   __syncthreads();
+  if constexpr (MX8) {
+    if (owner && tid < 32) {                               // the append: slot [n][pos] <- the MXFP8 rounding of the new k (lanes 0-15) and v (lanes 16-31)
+      const bool isv = tid >= 16;
+      const uint4 nv = *reinterpret_cast<const uint4*>((isv ? vnew : knew) + c * 8);
+      uint32_t w[4] = {nv.x, nv.y, nv.z, nv.w}, lo, hi;
+      uint32_t amax = mx8_amax8(w);
+      amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1));
+      amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2));
+      const int sb = mx8_scale_byte(amax);
+      mx8_encode8(w, sb, lo, hi);
+      uint8_t* q8 = reinterpret_cast<uint8_t*>(isv ? p.vc : p.kc) + (long)n * p.cstride + (long)pos * D + (long)h * HD;
+      *reinterpret_cast<uint2*>(q8 + c * 8) = make_uint2(lo, hi);
+      if ((c & 3) == 0) (isv ? p.vsc : p.ksc)[(long)n * p.sstride + (long)pos * SD + h * 4 + (c >> 2)] = (uint8_t)sb;
+    }
+  }
   float q[8], acc[8], m = -1e30f, l = 0.f;
 #pragma unroll
   for (int e = 0; e < 8; ++e) { q[e] = qs[c * 8 + e]; acc[e] = 0.f; }
   for (int jb = j0; jb < j1; jb += 16 * UN) {
     uint4 kk[UN], vv[UN];
+    uint32_t ksw[UN], vsw[UN];                            // MX8: kk / vv hold 8 bytes in .x / .y until the unpack, ksw / vsw the key's scale words
     long phys[UN];
     if constexpr (TABLE) {                              // the trip's table entries first: the K and V addresses wait for them
       const int32_t* srow = p.src + (long)n * p.ld_src;
@@ -85,9 +130,16 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecP p) {
     for (int u = 0; u < UN; ++u) {
       const int j = jb + u * 16 + g;
       kk[u] = make_uint4(0, 0, 0, 0); vv[u] = kk[u];
+      if constexpr (MX8) { ksw[u] = 0u; vsw[u] = 0u; }
       if (j < j1) {
         if (j == pos) { kk[u] = *reinterpret_cast<const uint4*>(knew + c * 8); vv[u] = *reinterpret_cast<const uint4*>(vnew + c * 8); }
-        else {
+        else if constexpr (MX8) {
+          const long prow = TABLE ? phys[u] : (long)n;
+          const long off = prow * p.cstride + (long)j * D + c * 8, soff = prow * p.sstride + (long)j * SD + h * 4;
+          const uint2 k2 = *reinterpret_cast<const uint2*>(k8 + off), v2 = *reinterpret_cast<const uint2*>(v8 + off);
+          kk[u].x = k2.x; kk[u].y = k2.y; vv[u].x = v2.x; vv[u].y = v2.y;
+          ksw[u] = *reinterpret_cast<const uint32_t*>(p.ksc + soff); vsw[u] = *reinterpret_cast<const uint32_t*>(p.vsc + soff);
+        } else {
           if constexpr (TABLE) {
             const long off = phys[u] * p.cstride + (long)j * D + c * 8;
             kk[u] = *reinterpret_cast<const uint4*>(kh + off); vv[u] = *reinterpret_cast<const uint4*>(vh + off);
@@ -99,8 +151,14 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecP p) {
     for (int u = 0; u < UN; ++u) {
       const int j = jb + u * 16 + g;
       float kf[8], vf[8], s = 0.f;
-      unpack8(kk[u], kf);
-      unpack8(vv[u], vf);
+      if (MX8 && j != pos && j < j1) {                     // a cached key of the packed cache (the new token's and a key beyond j1 are bf16 as in the other instances)
+        const int sh = 8 * (c >> 2);
+        mx8_unpack8(kk[u].x, kk[u].y, (int)((ksw[u] >> sh) & 0xffu), kf);
+        mx8_unpack8(vv[u].x, vv[u].y, (int)((vsw[u] >> sh) & 0xffu), vf);
+      } else {
+        unpack8(kk[u], kf);
+        unpack8(vv[u], vf);
+      }
 #pragma unroll
       for (int e = 0; e < 8; ++e) s = fmaf(q[e], kf[e], s);
       s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
@@ -160,17 +218,28 @@ __global__ __launch_bounds__(128) void decode_attn_merge_kernel(const float* __r
   out[(long)n * ldo + (long)h * 128 + tid] = f2bf(o / L);
 }
 
-// `table`: the entry point reads through `src` (a null `src` is then an error, not the plain route); after the checks it is `src != nullptr`
-int decode_attn_launch(bool table, const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+struct Mx8Scales { void *k, *v; int64_t stride_n; };      // the packed cache's scale bytes; the bf16 entry points pass none
+
+// `table`: the entry point reads through `src` (a null `src` is then an error, not the plain route); after the checks it is `src != nullptr`.
+// `mx`: the packed cache (llmseg_decode_attn_mxfp8), whose caches hold bytes: 8-byte rows instead of 16-byte ones, and the checks of its scales.
+int decode_attn_launch(bool table, const Mx8Scales* mx, const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                        const int32_t* pos_dev, long pos_stride, const int32_t* src, int64_t ld_src, int64_t capacity, int64_t N, int32_t heads, int32_t head_dim,
                        float scale, void* out, int64_t ldo, void* scratch, int64_t scratch_bytes, void* stream) {
-  const char* who = table ? "decode_attn_beams" : "decode_attn";
+  const char* who = mx ? "decode_attn_mxfp8" : table ? "decode_attn_beams" : "decode_attn";
   LL_CHECK(qkv && cos && sin && kcache && vcache && pos_dev && out && N > 0 && N < 65536 && heads > 0, "%s: bad arguments", who);
   LL_CHECK(head_dim == 128, "%s: head_dim 128 only%s", who, table ? "" : " (use llmseg_rope_kv_append + llmseg_attn_fwd otherwise)");
-  LL_CHECK((ld & 7) == 0 && (cache_stride_n & 7) == 0 && AL16(qkv) && AL16(kcache) && AL16(vcache), "%s: 16-byte alignment required", who);
+  if (mx) {
+    LL_CHECK((ld & 7) == 0 && AL16(qkv) && (cache_stride_n & 7) == 0 && ((uintptr_t)kcache & 7) == 0 && ((uintptr_t)vcache & 7) == 0,
+             "decode_attn_mxfp8: qkv 16-byte aligned, the byte caches and their sequence stride 8-byte aligned");
+    LL_CHECK(mx->k && mx->v && ((uintptr_t)mx->k & 3) == 0 && ((uintptr_t)mx->v & 3) == 0 && (mx->stride_n & 3) == 0 && mx->stride_n >= (int64_t)heads * 4,
+             "decode_attn_mxfp8: scales must be 4-byte aligned with a sequence stride %% 4 == 0 of at least heads * 4 bytes");
+    LL_CHECK(cache_stride_n >= (int64_t)heads * 128, "decode_attn_mxfp8: cache_stride_n %ld < heads * 128", (long)cache_stride_n);
+    LL_CHECK(pos_stride == 0 || pos_stride == 1, "decode_attn_mxfp8: pos_stride must be 0 (one position) or 1 (one per sequence)");
+  } else
+    LL_CHECK((ld & 7) == 0 && (cache_stride_n & 7) == 0 && AL16(qkv) && AL16(kcache) && AL16(vcache), "%s: 16-byte alignment required", who);
   if (table) {
-    LL_CHECK(src && ((uintptr_t)src & 3) == 0, "decode_attn_beams: src must be a 4-byte aligned int32 table");
-    LL_CHECK(capacity > 0 && ld_src >= capacity, "decode_attn_beams: ld_src %ld < capacity %ld", (long)ld_src, (long)capacity);
+    LL_CHECK(src && ((uintptr_t)src & 3) == 0, "%s: src must be a 4-byte aligned int32 table", who);
+    LL_CHECK(capacity > 0 && ld_src >= capacity, "%s: ld_src %ld < capacity %ld", who, (long)ld_src, (long)capacity);
   }
   int splits = 1;
   if (scratch) {
@@ -178,15 +247,17 @@ int decode_attn_launch(bool table, const void* qkv, int64_t ld, const float* cos
     while (splits > 1 && (int64_t)N * heads * splits * 130 * 4 > scratch_bytes) --splits;
   }
   DecP p{(const bf16_t*)qkv, (long)ld, cos, sin, (bf16_t*)kcache, (bf16_t*)vcache, (long)cache_stride_n, pos_dev, pos_stride, heads, splits, scale,
-         (bf16_t*)out, (long)ldo, (float*)scratch, src, (long)ld_src};
+         (bf16_t*)out, (long)ldo, (float*)scratch, src, (long)ld_src, mx ? (uint8_t*)mx->k : nullptr, mx ? (uint8_t*)mx->v : nullptr, mx ? (long)mx->stride_n : 0L};
   const dim3 grid(heads * splits, (unsigned)N);
-  if (table) LL_LAUNCH_KERNEL(decode_attn_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  else LL_LAUNCH_KERNEL(decode_attn_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  if (mx && table) LL_LAUNCH_KERNEL((decode_attn_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  else if (mx) LL_LAUNCH_KERNEL((decode_attn_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  else if (table) LL_LAUNCH_KERNEL((decode_attn_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  else LL_LAUNCH_KERNEL((decode_attn_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
   LL_LAUNCH_CHECK(who);
   if (splits > 1) {
     LL_LAUNCH_KERNEL(decode_attn_merge_kernel, dim3(heads, (unsigned)N), dim3(128), 0, (hipStream_t)stream, (const float*)scratch, heads, splits,
                      (bf16_t*)out, (long)ldo);
-    LL_LAUNCH_CHECK(table ? "decode_attn_beams_merge" : "decode_attn_merge");
+    LL_LAUNCH_CHECK(mx ? "decode_attn_mxfp8_merge" : table ? "decode_attn_beams_merge" : "decode_attn_merge");
   }
   return LLMSEG_OK;
 }
@@ -196,7 +267,7 @@ int decode_attn_launch(bool table, const void* qkv, int64_t ld, const float* cos
 extern "C" int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                                   const int32_t* pos_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
                                   void* scratch, int64_t scratch_bytes, void* stream) {
-  return decode_attn_launch(false, qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_dev, 0, nullptr, 0, 0, N, heads, head_dim, scale, out, ldo, scratch, scratch_bytes,
+  return decode_attn_launch(false, nullptr, qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_dev, 0, nullptr, 0, 0, N, heads, head_dim, scale, out, ldo, scratch, scratch_bytes,
                             stream);
 }
 
@@ -204,7 +275,7 @@ extern "C" int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos,
 extern "C" int llmseg_decode_attn_rows(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                                        const int32_t* pos_rows_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
                                        void* scratch, int64_t scratch_bytes, void* stream) {
-  return decode_attn_launch(false, qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_rows_dev, 1, nullptr, 0, 0, N, heads, head_dim, scale, out, ldo, scratch,
+  return decode_attn_launch(false, nullptr, qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_rows_dev, 1, nullptr, 0, 0, N, heads, head_dim, scale, out, ldo, scratch,
                             scratch_bytes, stream);
 }
 
@@ -212,6 +283,16 @@ extern "C" int llmseg_decode_attn_rows(const void* qkv, int64_t ld, const float*
 extern "C" int llmseg_decode_attn_beams(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                                         const int32_t* pos_rows_dev, const int32_t* src, int64_t ld_src, int64_t capacity, int64_t N, int32_t heads,
                                         int32_t head_dim, float scale, void* out, int64_t ldo, void* scratch, int64_t scratch_bytes, void* stream) {
-  return decode_attn_launch(true, qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_rows_dev, 1, src, ld_src, capacity, N, heads, head_dim, scale, out, ldo, scratch,
+  return decode_attn_launch(true, nullptr, qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_rows_dev, 1, src, ld_src, capacity, N, heads, head_dim, scale, out, ldo, scratch,
                             scratch_bytes, stream);
+}
+
+// the same step on an MXFP8 cache (E4M3 bytes + E8M0 scale bytes): pos_stride 0 = one position for every sequence, 1 = one per sequence; src nullable
+extern "C" int llmseg_decode_attn_mxfp8(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                                        void* kscale, void* vscale, int64_t scale_stride_n, const int32_t* pos_dev, int64_t pos_stride, const int32_t* src,
+                                        int64_t ld_src, int64_t capacity, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
+                                        void* scratch, int64_t scratch_bytes, void* stream) {
+  const Mx8Scales mx{kscale, vscale, scale_stride_n};
+  return decode_attn_launch(src != nullptr, &mx, qkv, ld, cos, sin, kcache, vcache, cache_stride_n, pos_dev, (long)pos_stride, src, ld_src, capacity, N, heads, head_dim,
+                            scale, out, ldo, scratch, scratch_bytes, stream);
 }

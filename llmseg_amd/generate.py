@@ -70,6 +70,26 @@ def _weight_mode(weight_bits, weight_format, fuse_decode):
     return weight_format
 
 
+def _check_kv(model, kv_format, kv_cache, fuse_decode):
+    """generate()'s KV-cache arguments, checked -> what the decode state is keyed by on top of today's key: () for the bf16 cache, else ("kv", kv_format, kv_cache)."""
+    if kv_format not in (None, "mxfp8"):
+        raise ValueError(f"kv_format must be None (a bf16 KV cache) or 'mxfp8' (E4M3 elements with one E8M0 scale per 32), got {kv_format!r}")
+    if kv_cache not in ("packed", "bf16"):
+        raise ValueError(f"kv_cache must be 'packed' or 'bf16', got {kv_cache!r}")
+    if kv_format is None:
+        if kv_cache != "packed":
+            raise ValueError("kv_cache='bf16' needs kv_format: it is the yardstick of a quantised cache (the same values held in bf16)")
+        return ()
+    if not fuse_decode:
+        raise ValueError(f"kv_format={kv_format!r} needs fuse_decode=True (the packed cache is built into the fused decode step only)")
+    c = model.config.llama
+    if c.head_dim != 128:
+        raise ValueError(f"kv_format={kv_format!r} needs head_dim 128, got {c.head_dim}: the two-launch route is out of scope")
+    if c.hidden % 32:
+        raise ValueError(f"kv_format={kv_format!r} needs hidden % 32 == 0 (one scale per 32 elements), got hidden = {c.hidden}")
+    return ("kv", kv_format, kv_cache)
+
+
 def _check_controls(model, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens, num_beams):
     """generate()'s logits controls, checked -> None with all four at their defaults (no logits-processor launch), else the four by name, suppress_tokens as a list."""
     if repetition_penalty == 1.0 and no_repeat_ngram_size == 0 and min_new_tokens == 0 and suppress_tokens is None:
@@ -282,11 +302,17 @@ class BeamBook:
 class DecodeState:
     """Everything a decode step touches, at fixed addresses (so the step can be captured once and replayed): the KV cache
     [layers][N, capacity, H] bf16 x 2, the device-side position {pos, pos + 1} (or one position per sequence, pos_rows, when the prompts
-    differ in length), the step's input embeddings and its outputs."""
+    differ in length), the step's input embeddings and its outputs.  kv = ("kv", "mxfp8", "packed"): K and V are uint8 E4M3 codes, with their E8M0 scale bytes
+    ks, vs [layers][N, capacity, H / 32]; ("kv", "mxfp8", "bf16"): the bf16 cache, which then holds x_hat (the yardstick of the packed cache)."""
 
-    def __init__(self, layers, N, cap, H, V, device):
-        self.k = torch.empty((layers, N, cap, H), device=device, dtype=BF16)
-        self.v = torch.empty((layers, N, cap, H), device=device, dtype=BF16)
+    def __init__(self, layers, N, cap, H, V, device, kv=()):
+        self.kv_format, self.kv_packed = (kv[1], kv[2] == "packed") if kv else (None, False)
+        self.k = torch.empty((layers, N, cap, H), device=device, dtype=torch.uint8 if self.kv_packed else BF16)
+        self.v = torch.empty_like(self.k)
+        self.ks = self.vs = None
+        if self.kv_packed:
+            self.ks = torch.empty((layers, N, cap, H // 32), device=device, dtype=torch.uint8)
+            self.vs = torch.empty_like(self.ks)
         self.pos = torch.zeros((2,), device=device, dtype=torch.int32)       # [0] = position of the token being fed, [1] = keys present after it
         self.pos_rows = torch.zeros((N,), device=device, dtype=torch.int32)  # ragged prompts: position of the token being fed, per sequence
         self.x = torch.empty((N, H), device=device, dtype=BF16)
@@ -363,8 +389,16 @@ class GenerateMixin:
         c = self.config.llama
         hd, heads, H = c.head_dim, c.heads, st.H
         if st.fused and hd == 128:                             # one launch (+ the split's merge); ragged: every sequence at its own position (RoPE angle, cache slot, key count)
-            ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows if st.ragged else st.pos, heads, hd, out=att, scratch=scratch, per_row=st.ragged,
-                            beam_src=st.beam_src)
+            pos = st.pos_rows if st.ragged else st.pos
+            if st.kv_packed:                                   # the same step on the MXFP8 cache: slot [n][pos] receives the rounding of the new k / v
+                ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], pos, heads, hd, out=att, scratch=scratch, per_row=st.ragged, beam_src=st.beam_src,
+                                k_scale=st.ks[i], v_scale=st.vs[i])
+                return
+            ops.decode_attn(qkv, cos, sin, st.k[i], st.v[i], pos, heads, hd, out=att, scratch=scratch, per_row=st.ragged, beam_src=st.beam_src)
+            if st.kv_format is not None:                       # kv_cache="bf16", the yardstick: slot [n][pos_n] <- its x_hat, in place, at the position the step reads
+                row0 = pos if st.ragged else pos[:1]
+                ops.kv_quantize_mxfp8(st.k[i], x_hat=st.k[i], row0=row0, rows=1)
+                ops.kv_quantize_mxfp8(st.v[i], x_hat=st.v[i], row0=row0, rows=1)
         else:
             ld = qkv.stride(0)
             ops.rope_kv_append_(qkv, cos, sin, st.k[i], st.v[i], st.pos, heads, hd)       # q, k rotated at the device-side position; k, v -> cache
@@ -520,10 +554,11 @@ class GenerateMixin:
             st.graph = g                                        # capture records, it does not execute: fall through to the replay
         st.graph.replay()
 
-    def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, mode, fused, key):
+    def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, mode, fused, key, kv=()):
         """What every generate() route does before its loop: the prompts (input_ids [N, L], trimmed; attention_mask = the ragged call's mask, else None) through the prefill
         in the call's weight mode (`_weight_mode`), K and V of prompt n into physical row n * rows of the decode state of N * rows rows (rows = 1, or the beams per prompt), the state made ready
-        for the call's route.  The states are kept per (N * rows, capacity) + key.  -> (state, final-norm hidden [N, T, H], T, embedding weights, lm_head weights)."""
+        for the call's route.  The states are kept per (N * rows, capacity) + key + kv (kv = `_check_kv`'s: a quantised cache is a state of its own, and K / V go into it
+        through `ops.kv_quantize_mxfp8`).  -> (state, final-norm hidden [N, T, H], T, embedding weights, lm_head weights)."""
         self.prepare()
         c = self.config
         cl = c.llama
@@ -539,16 +574,25 @@ class GenerateMixin:
         embeds = F.embed_splice(input_ids.to(dev).contiguous(), emb_w, proj[1:], Pn, (Pn + 1) * H, plan.tok_index)
         cap = (T + max_new_tokens + 63) // 64 * 64
         states = self.__dict__.setdefault("_decode_states", {})
+        key = key + kv
         st = states.get((N * rows, cap) + key)
         if st is None:
-            st = states[(N * rows, cap) + key] = DecodeState(cl.layers, N * rows, cap, H, cl.vocab, dev)
+            st = states[(N * rows, cap) + key] = DecodeState(cl.layers, N * rows, cap, H, cl.vocab, dev, kv=kv)
 
         # ragged prompts: K and V are copied for [:, :T] of every row.  The slots at or beyond a row's own T_i = L_i - 1 + Pn then hold the padding's
         # K / V (and, past T, whatever an earlier call left): garbage that is never read, because the step that feeds a row's token at position
         # pos writes cache[pos] itself and attends to keys 0 .. pos only -- a slot is overwritten before the row's key count reaches it.
         def keep_kv(i, qkv):                                   # qkv [N*T, 3H] after the in-place RoPE of q and k
-            st.k[i, ::rows, :T].copy_(qkv[:, H:2 * H].view(N, T, H))
-            st.v[i, ::rows, :T].copy_(qkv[:, 2 * H:3 * H].view(N, T, H))
+            k, v = qkv[:, H:2 * H].view(N, T, H), qkv[:, 2 * H:3 * H].view(N, T, H)
+            if st.kv_format is None:
+                st.k[i, ::rows, :T].copy_(k)
+                st.v[i, ::rows, :T].copy_(v)
+            elif st.kv_packed:                                 # through the quantiser: one launch per layer and tensor
+                ops.kv_quantize_mxfp8(k, q=st.k[i, ::rows, :T], scale=st.ks[i, ::rows, :T])
+                ops.kv_quantize_mxfp8(v, q=st.v[i, ::rows, :T], scale=st.vs[i, ::rows, :T])
+            else:                                              # the yardstick: the bf16 cache holds x_hat
+                ops.kv_quantize_mxfp8(k, x_hat=st.k[i, ::rows, :T])
+                ops.kv_quantize_mxfp8(v, x_hat=st.v[i, ::rows, :T])
         if mode is None:
             st.qw = None
             hidden_p = self._llama(embeds, plan.key_mask, F, kv_out=keep_kv)      # [N, T, H]
@@ -565,7 +609,7 @@ class GenerateMixin:
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
                  weight_bits=None, attention_mask=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None,
                  return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False, return_beam_scores=False, beam_cache="indirect", _beam_trace=None,
-                 weight_format=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None):
+                 weight_format=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, kv_format=None, kv_cache="packed"):
         """Greedy generation (or sampling: do_sample, or beam search: num_beams, both below).  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
         IMAGE_TOKEN_INDEX each.
         -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
@@ -625,23 +669,39 @@ class GenerateMixin:
         weight_format, attention_mask and do_sample all compose.  With all four at their defaults no history is built, `ops.logits_process` is never called and every
         route is launch for launch the one above.  Measured at Llama-7B (profiles/generation_controls.md): the four controls add 0.007 / -0.001 ms per token at 1 / 8
         sequences (inside the run-to-run spread) where Hugging Face's processor objects on the device add 0.104 / 0.122.  Out of scope (ValueError): any of the four with
-        num_beams >= 2 -- HF applies processors to the log-softmax there, not to the logits: another rule and another `beam_step`."""
+        num_beams >= 2 -- HF applies processors to the log-softmax there, not to the logits: another rule and another `beam_step`.
+        kv_format = "mxfp8" (opt-in; needs fuse_decode, head_dim 128 and hidden % 32 == 0): the KV cache holds OCP MXFP8 -- E4M3 bytes with one power-of-two E8M0 scale
+        byte per 32 values (`ops.kv_quantize_mxfp8`; the rule is stated in include/llmseg_hip.h) -- 264 KiB instead of 512 KiB per cached token and sequence at
+        Llama-7B.  The prefill is untouched (prompt positions attend among themselves in bf16) and writes K and V through the quantiser, one launch per layer and
+        tensor; every decode step runs the MXFP8 instance of the decode-attention kernel (`llmseg_decode_attn_mxfp8`) on all three position routes (uniform,
+        attention_mask rows, beams with either beam_cache): the new token's k / v enter the step as bf16 and are stored rounded, earlier keys are decoded on load.
+        It composes with weight_bits, weight_format, do_sample, the four logits controls, num_beams and use_graph.  kv_cache = "bf16" (needs kv_format) is the
+        yardstick: the same model on a bf16 cache that holds x_hat = element * 2^e (the prefill writes x_hat, each step runs the bf16 kernel and then rewrites slot
+        [n][pos_n] in place, inside the captured step) -- the same bits as the packed cache at bf16 traffic.  The states of these routes are keyed apart
+        (`("kv", kv_format, kv_cache)` joins the key), so a default call never meets them.  Measured at Llama-7B, 64-token prompt, 321 .. 353 keys, in one session,
+        alternating (profiles/kv_mxfp8.md): the packed cache is NOT faster at these shapes -- 3.32 / 5.09 ms per token at 1 / 8 sequences against 3.33 / 5.03 with the
+        bf16 cache, 5.31 / 6.60 at 3 prompts x 4 / x 16 beams against 5.19 / 6.00 (with MXFP4 weights 2.10 / 3.44 / 5.49 / 14.80 against 2.06 / 3.40 / 5.38 / 14.20): the
+        kernel keeps the bf16 instance's lane mapping and spends on the unpack what it saves on the load; what the format buys today is the memory (half the cache).
+        After 512 more tokens (833 .. 865 keys) the picture is the same: 3.40 / 5.66 against 3.40 / 5.53 at 1 / 8 sequences, 8.43 against 7.28 at 3 x 16 beams.
+        The quantiser adds nothing measurable to the prefill.  Accuracy: E4M3 keeps four significant bits of every cached value; on the tiny test model the
+        hidden states differ from the oracle by up to 0.38 (bf16 cache: 0.15) at |h| <= 6.1."""
         controls = _check_controls(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens, num_beams)
         _check_beams(self, num_beams, length_penalty, early_stopping, return_beam_scores, beam_cache, _beam_trace, do_sample, fuse_decode)
         sampling = _check_sampling(do_sample, temperature, top_k, top_p, seed, uniforms, return_logprobs, input_ids, max_new_tokens)
         mode = _weight_mode(weight_bits, weight_format, fuse_decode)
+        kv = _check_kv(self, kv_format, kv_cache, fuse_decode)
         fill = 0 if pad_token_id is None else int(pad_token_id)      # what finished rows and the padding hold
         if num_beams >= 2:
             return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, fill, use_graph, mode, attention_mask, num_beams, float(length_penalty),
-                                        early_stopping, return_beam_scores, beam_cache, _beam_trace)
+                                        early_stopping, return_beam_scores, beam_cache, _beam_trace, kv)
         input_ids, attention_mask, lens = _row_prompts(self, input_ids, attention_mask, fuse_decode, fill, controls, max_new_tokens)
         return self._generate_rows(images_clip, input_ids, attention_mask, lens, max_new_tokens, eos_token_id, pad_token_id, fill, use_graph, bool(fuse_decode), mode,
-                                   sampling, controls)
+                                   sampling, controls, kv)
 
-    def _generate_rows(self, images_clip, input_ids, attention_mask, lens, max_new_tokens, eos_token_id, pad_token_id, fill, use_graph, fused, mode, sampling, controls):
+    def _generate_rows(self, images_clip, input_ids, attention_mask, lens, max_new_tokens, eos_token_id, pad_token_id, fill, use_graph, fused, mode, sampling, controls, kv=()):
         """`generate(num_beams=1)`: the arguments are checked there.  One token per row and step: the pick (`_make_pick`: arg-max or sampling, after the controls),
         the stop test, the decode step on the picked tokens; where positions, hidden states and sequences go is the layout's (uniform, or ragged: lens is not None)."""
-        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, mode, fused, ())
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, mode, fused, (), kv)
         layout = _uniform_rows(st, hidden_p, lm_w, max_new_tokens) if lens is None else _ragged_rows(st, hidden_p, lm_w, max_new_tokens, lens, self.config.n_img_tokens, fill)
         logits, store, pack = layout
         seqs, n_new = [input_ids.to(self.device_)], 0
@@ -661,7 +721,7 @@ class GenerateMixin:
         return res + (torch.cat([lp[:, None] for lp in live.logprobs], 1),) if sampling is not None and sampling["return_logprobs"] else res
 
     def _generate_beams(self, images_clip, input_ids, max_new_tokens, eos_token_id, fill, use_graph, mode, attention_mask, B, length_penalty, early_stopping,
-                        return_beam_scores, beam_cache, trace):
+                        return_beam_scores, beam_cache, trace, kv=()):
         """`generate(num_beams=B >= 2)`: the arguments are checked there.  The device loop; hypotheses, the done rule and the winners are the `BeamBook`'s."""
         if attention_mask is not None:
             input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
@@ -669,7 +729,7 @@ class GenerateMixin:
                 raise ValueError("num_beams >= 2 with prompts of different lengths (an attention_mask that is ragged after trimming) is out of scope")
         indirect = beam_cache == "indirect"
         # a state of its own: a greedy call on N * B sequences never meets a beam call's graph
-        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, None, B, max_new_tokens, mode, True, ("beams", beam_cache))
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, None, B, max_new_tokens, mode, True, ("beams", beam_cache), kv)
         dev = self.device_
         N, L = input_ids.shape
         R, H = N * B, self.config.llama.hidden
@@ -708,8 +768,8 @@ class GenerateMixin:
             scores = out["next_scores"]
             if not indirect:                                   # the yardstick: move every layer's K and V to the beams' new rows
                 gidx = row0 + out["parent"]
-                st.k.copy_(st.k.index_select(1, gidx))
-                st.v.copy_(st.v.index_select(1, gidx))
+                for t in (st.k, st.v) + ((st.ks, st.vs) if st.kv_packed else ()):      # (a packed cache: bytes and scale bytes)
+                    t.copy_(t.index_select(1, gidx))
             st.x.copy_(ops.gather_rows(emb_w, out["next_token"]))
             self._decode_step(st, use_graph)
             hids.append(st.hidden.clone())

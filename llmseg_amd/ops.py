@@ -426,12 +426,43 @@ def rope_kv_append_(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim):
     return qkv
 
 
-def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=None, scale=None, scratch=None, per_row=False, beam_src=None):
+def kv_quantize_mxfp8(x, q=None, scale=None, x_hat=None, row0=None, rows=None):
+    """MXFP8 quantisation of the rows of x bf16 [B, R, D] (any batch and row stride, D contiguous and % 32 == 0) in ONE launch (`llmseg_kv_quantize_mxfp8`; the rule
+    is stated in include/llmseg_hip.h): q uint8 [B, R', D] E4M3 codes and scale uint8 [B, R', D / 32] E8M0 bytes (given as a pair), and / or x_hat bf16 [B, R', D]
+    = element * 2^e.  x_hat may be x itself.  row0 (int32 device tensor of 1 or B elements, None = 0): row r of batch b is row row0[b] + r of EVERY operand, so the
+    operands may have more rows than the R = `rows` the call works on (None: the smallest row count among them).  -> (q, scale, x_hat) as given."""
+    _req(x)
+    assert x.dim() == 3 and x.stride(2) == 1 and x.shape[2] % 32 == 0, (x.shape, x.stride())
+    B, _, D = x.shape
+    assert (q is None) == (scale is None) and (q is not None or x_hat is not None)
+    ops_ = [x]
+    if q is not None:
+        assert q.is_cuda and q.dtype == torch.uint8 and q.dim() == 3 and q.shape[0] == B and q.shape[2] == D and q.stride(2) == 1
+        assert scale.is_cuda and scale.dtype == torch.uint8 and scale.dim() == 3 and scale.shape[0] == B and scale.shape[2] == D // 32 and scale.stride(2) == 1
+        assert scale.shape[1] == q.shape[1]
+        ops_ += [q, scale]
+    if x_hat is not None:
+        assert _req(x_hat).dim() == 3 and x_hat.shape[0] == B and x_hat.shape[2] == D and x_hat.stride(2) == 1
+        ops_.append(x_hat)
+    R = min(t.shape[1] for t in ops_) if rows is None else int(rows)
+    assert 1 <= R <= min(t.shape[1] for t in ops_)
+    if row0 is not None:
+        assert row0.is_cuda and row0.dtype == torch.int32 and row0.numel() in (1, B) and row0.is_contiguous()
+    st = lambda t: (0, 0) if t is None else (t.stride(0) if B > 1 else R * t.stride(1), t.stride(1))
+    _lib.check(_lib.load().llmseg_kv_quantize_mxfp8(_ptr(x), *st(x), _ptr(q), *st(q), _ptr(scale), *st(scale), _ptr(x_hat), *st(x_hat), _ptr(row0),
+                                                    0 if row0 is None or row0.numel() == 1 else 1, B, R, D, _stream()), "kv_quantize_mxfp8")
+    return q, scale, x_hat
+
+
+def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=None, scale=None, scratch=None, per_row=False, beam_src=None, k_scale=None, v_scale=None):
     """Decode step in one launch (+ merge): k rotated / v copied into the caches at position *pos_dev, out[n] = attention of the rotated q
     over the pos + 1 cached keys.  head_dim 128.  scratch: fp32 buffer from decode_attn_scratch (None = one workgroup per head).
     per_row: pos_dev is int32 [N], sequence n rotates, appends and attends at its own position pos_dev[n] (llmseg_decode_attn_rows).
     beam_src (needs per_row): int32 [N, >= capacity] table, key t < pos of row n is read from physical cache row beam_src[n, t]
-    (llmseg_decode_attn_beams; entries are trusted to lie in [0, N))."""
+    (llmseg_decode_attn_beams; entries are trusted to lie in [0, N)).
+    k_scale, v_scale (uint8 [N, capacity, heads * head_dim / 32], given as a pair): the caches are MXFP8 -- uint8 E4M3 codes with these E8M0 scale bytes
+    (`kv_quantize_mxfp8`) -- and the call goes to llmseg_decode_attn_mxfp8: slot [n][pos] receives the MXFP8 rounding of the new k / v, which this step still
+    uses as bf16; per_row and beam_src compose as above."""
     N = qkv.shape[0]
     assert kcache.shape == vcache.shape and kcache.shape[0] == N and kcache.stride(1) == heads * head_dim and pos_dev.dtype == torch.int32
     if out is None:
@@ -442,6 +473,18 @@ def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=Non
     if beam_src is not None:
         assert beam_src.is_cuda and beam_src.dtype == torch.int32 and beam_src.dim() == 2 and beam_src.shape[0] == N and beam_src.stride(1) == 1
         name, extra = "decode_attn_beams", (_ptr(beam_src), max(beam_src.stride(0), beam_src.shape[1]) if N == 1 else beam_src.stride(0), kcache.shape[1])
+    if k_scale is not None or v_scale is not None:
+        assert kcache.dtype == vcache.dtype == torch.uint8 and kcache.is_cuda and vcache.is_cuda and vcache.stride(1) == kcache.stride(1) and vcache.stride(0) == kcache.stride(0)
+        for s in (k_scale, v_scale):
+            assert s is not None and s.is_cuda and s.dtype == torch.uint8 and s.shape == (N, kcache.shape[1], heads * head_dim // 32) and s.stride(2) == 1 and s.stride(1) == s.shape[2]
+        assert k_scale.stride(0) == v_scale.stride(0)
+        _lib.check(_lib.load().llmseg_decode_attn_mxfp8(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(k_scale), _ptr(v_scale),
+                                                        k_scale.stride(0), _ptr(pos_dev), 1 if per_row else 0, *(extra or (None, 0, 0)), N, heads, head_dim,
+                                                        float(scale if scale is not None else head_dim ** -0.5), _ptr(out), out.stride(0),
+                                                        _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0, _stream()),
+                   "decode_attn_mxfp8")
+        return out
+    assert kcache.dtype == BF16, kcache.dtype
     _lib.check(getattr(_lib.load(), "llmseg_" + name)(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), kcache.stride(0), _ptr(pos_dev), *extra,
                                                        N, heads, head_dim, float(scale if scale is not None else head_dim ** -0.5), _ptr(out), out.stride(0),
                                                        _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,

@@ -180,19 +180,20 @@ class SamDecoderMixin:
     def evaluate(self, images_clip, images, input_ids, resize_list, original_size_list, max_new_tokens=32, tokenizer=None,
                  eos_token_id=2, pad_token_id=0, weight_bits=None, attention_mask=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None,
                  uniforms=None, num_beams=1, length_penalty=1.0, early_stopping=False, weight_format=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                 min_new_tokens=0, suppress_tokens=None):
+                 min_new_tokens=0, suppress_tokens=None, kv_format=None):
         """`LISAForCausalLM.evaluate` (LISA.py:477-559): greedy generation, [SEG] embeddings, SAM image embedding, one mask per [SEG]
         token through the prompt encoder + mask decoder, masks resized to the original image.  -> (output_ids, [fp32 [n_seg, H, W]]).
         weight_bits, weight_format: handed to `generate` (8 = int8 weight-only decode, "mxfp4" = MXFP4 weight-only decode; None = bf16).  attention_mask: handed to `generate` (right-padded prompts of
         different lengths; output_ids is then packed per row as `generate` describes).  do_sample, temperature, top_k, top_p, seed, uniforms: handed to
         `generate` (sampling instead of the arg-max; top_k=0 means off).  num_beams, length_penalty, early_stopping: handed to `generate` (beam search).
-        repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens: handed to `generate` (logits processors before the pick)."""
+        repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens: handed to `generate` (logits processors before the pick).
+        kv_format: handed to `generate` ("mxfp8" = the MXFP8 KV cache; None = bf16)."""
         assert self.config.backbone == "sam", "evaluate() decodes masks from the SAM image embedding"
         output_ids, hidden = self.generate(images_clip, input_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                            weight_bits=weight_bits, attention_mask=attention_mask, do_sample=do_sample, temperature=temperature,
                                            top_k=top_k, top_p=top_p, seed=seed, uniforms=uniforms, num_beams=num_beams, length_penalty=length_penalty,
                                            early_stopping=early_stopping, weight_format=weight_format, repetition_penalty=repetition_penalty,
-                                           no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)
+                                           no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, kv_format=kv_format)
         pred_embeddings = self.seg_embeddings(output_ids, hidden)
         g2 = self.config.sam.grid ** 2
         assert g2 == 4096 and self.config.sam.out_chans == 256, "the mask decoder is built for the 64 x 64 x 256 embedding (build_sam.py:63-66)"
