@@ -32,9 +32,9 @@ enum { LLMSEG_ACT_NONE = 0, LLMSEG_ACT_RELU = 1, LLMSEG_ACT_GELU = 2, LLMSEG_ACT
  * so a binding written against an older header (fields were appended in every round) fails loudly instead of having the library read
  * past the caller's struct.  llmseg_struct_size(which) returns the library's sizeof (0 = llmseg_gemm_args, 1 = llmseg_attn_args,
  * 2 = llmseg_attn_bwd_args, 3 = llmseg_dropout, 4 = llmseg_gemm_w8_args, 5 = llmseg_lora_down_args; -1 for an unknown index) so a binding can assert at load time;
- * llmseg_version() is bumped whenever a struct or a signature changes (21: llmseg_kv_quantize_mxfp8, llmseg_decode_attn_mxfp8; 20: llmseg_logits_process; 19: llmseg_quantize_rows_mxfp4, llmseg_gemm_mxfp4 and llmseg_gemm_mxfp4_args; 18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
+ * llmseg_version() is bumped whenever a struct or a signature changes (22: llmseg_decode_attn_chunk, llmseg_lookup_draft, llmseg_lookup_accept; 21: llmseg_kv_quantize_mxfp8, llmseg_decode_attn_mxfp8; 20: llmseg_logits_process; 19: llmseg_quantize_rows_mxfp4, llmseg_gemm_mxfp4 and llmseg_gemm_mxfp4_args; 18: llmseg_decode_attn_beams, llmseg_beam_step; 17: llmseg_lora_down takes llmseg_lora_down_args and replaces llmseg_lora_down_ws / _parts / _pack; 16: llmseg_sample_tokens; 15: llmseg_sam_dense_prompt, llmseg_sam_prompt_tokens; 14: llmseg_decode_attn_rows; 13: llmseg_quantize_rows_i8, llmseg_gemm_w8 and llmseg_gemm_w8_args; 12: llmseg_rle_encode, llmseg_rle_parse and their workspace queries; 11: llmseg_image_resize_u8_filter, llmseg_clip_preprocess, llmseg_mask_union; 10: llmseg_linear_bwd; 9: llmseg_attn_args.win_grid / win_nw / pad_q / pad_k / pad_v; 7: the fp32-activation head entry points; 4: the reduction entry points take a workspace; 5 = this header:
  * llmseg_dropout.seg_rows; 6: llmseg_gemm_args.norm_w / norm_eps / norm_out / ldn). */
-#define LLMSEG_ABI_VERSION 21
+#define LLMSEG_ABI_VERSION 22
 
 /* Determinism (round 4).  No kernel adds floating-point numbers with atomics: every sum whose terms come from several workgroups is
  * written as per-workgroup partials into CALLER-OWNED scratch (`workspace`, `workspace_bytes`; any device memory, 256-byte aligned, not
@@ -462,6 +462,55 @@ int llmseg_decode_attn_mxfp8(const void* qkv, int64_t ld, const float* cos, cons
                              void* kscale, void* vscale, int64_t scale_stride_n, const int32_t* pos_dev, int64_t pos_stride, const int32_t* src /* nullable */,
                              int64_t ld_src, int64_t capacity, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,
                              void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens = k)): Q = k + 1 tokens per sequence and step, THREE entry points ----
+ * A step feeds sequence n its last emitted token and up to k draft tokens as the step rows n * Q .. n * Q + Q - 1, verifies the drafts against the step's own
+ * arg-maxes and keeps the longest confirmed prefix plus one more token.  Every emitted token is the arg-max of the logits computed at the position in front of
+ * it: the result is a greedy continuation.
+ *
+ * llmseg_decode_attn_chunk: llmseg_decode_attn_rows for Q tokens per sequence (bf16 cache, head_dim 128, 1 <= Q <= LLMSEG_DECODE_CHUNK_MAX).  qkv [N * Q][ld];
+ * with pos = pos_rows_dev[n], token j of sequence n is rotated at pos + j (cos / sin fp32 [capacity][64]), its k (rotated) and v are written to cache slot
+ * [n][pos + j], and out[n * Q + j] = softmax over the keys 0 .. pos + j (the chunk is causal within itself).  The bits written to the cache are those Q successive
+ * llmseg_decode_attn_rows steps write; no other cache element is touched; a slot at or beyond `capacity` is not written (the caller keeps pos + Q <= capacity).
+ * A cached K or V row is loaded once and serves all Q queries; the Q new rows are taken from LDS by every workgroup of the head and stored by exactly one.  Key
+ * split and merge are llmseg_decode_attn's; scratch (optional): >= N * Q * heads * splits * 130 * 4 bytes for splits = min(16, 256 / (N * heads)), fewer
+ * splits if it is smaller.  Slots beyond the position the caller moves to afterwards hold keys of rejected tokens: the next step overwrites Q slots from the new
+ * position on before any query's key count reaches them.  Checked before the launch: what llmseg_decode_attn_rows checks, 1 <= Q <= LLMSEG_DECODE_CHUNK_MAX,
+ * N * Q < 65536, Q <= capacity, cache_stride_n >= capacity * heads * 128, ld >= 3 * heads * 128, ldo >= heads * 128. */
+#define LLMSEG_DECODE_CHUNK_MAX 8
+int llmseg_decode_attn_chunk(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                             const int32_t* pos_rows_dev, int64_t capacity, int64_t N, int32_t Q, int32_t heads, int32_t head_dim, float scale,
+                             void* out, int64_t ldo, void* scratch, int64_t scratch_bytes, void* stream);
+/* llmseg_lookup_draft, ONE launch (one workgroup per row): the draft of Hugging Face's PromptLookupCandidateGenerator.get_candidates (no logits processor, no eos
+ * cut) on the row's history h[0 .. len) = hist[n][0 .. hist_len[n]) -- the buffer of llmseg_logits_process: prompt ids as given, the <image> placeholder included,
+ * then the emitted tokens; ld_hist <= LLMSEG_LOGITS_HIST_CAP.  For g = min(max_ngram, len - 1) down to 1: among the windows h[i .. i + g) equal to the last g ids
+ * (raw int64 values) whose continuation is not empty (i + g < len: the tail itself is no match) the EARLIEST is taken, and the first g that has one ends the
+ * search.  The draft is h[i + g ..), at most k ids, cut at the end of the history, at max_new_tokens - count[n] - 1 ids (the step emits the accepted drafts and
+ * one more token) and before the first id outside [0, V).  No match: draft length 0.  A row with unfinished[n] == 0 or count[n] >= max_new_tokens drafts nothing.
+ * forced (nullable, int64 [N][ld_forced]; a test hook): the draft is forced[n][count[n] ..) instead of the lookup, under the same three cuts (ld_forced for the
+ * end of the history).  Written: tok [N][k + 1] = the last id of the history (the last emitted token), the draft, then pad_token; draft_len [N].
+ * Checked before the launch: non-NULL pointers and their alignment, 1 <= N, V < 2^31, 1 <= ld_hist <= LLMSEG_LOGITS_HIST_CAP, 0 <= k < LLMSEG_DECODE_CHUNK_MAX,
+ * max_ngram >= 1, max_new_tokens >= 1. */
+int llmseg_lookup_draft(const int64_t* hist, int64_t ld_hist, const int32_t* hist_len, const int32_t* count, const int32_t* unfinished, int64_t N,
+                        int32_t k, int32_t max_ngram, int32_t max_new_tokens, int64_t V, int64_t pad_token, const int64_t* forced /* nullable */,
+                        int64_t ld_forced, int64_t* tok, int32_t* draft_len, void* stream);
+/* llmseg_lookup_accept, TWO launches (the arg-max of every step row; one thread per sequence for the rule): logits bf16 [N * Q][ldl], V entries a row.  With
+ * m_j = argmax(logits[n * Q + j]) -- the lowest index among equal values, a NaN as the largest value: torch.argmax -- and d = draft_len[n] (0 without tok):
+ *   a = the number of leading drafts j = 1 .. d with tok[n][j] == m_(j - 1);
+ *   the row emits m_0 .. m_a (the accepted drafts and one more token), cut at max_new_tokens - count[n] tokens and after the first eos_token (-1 = none);
+ *   a row with unfinished[n] == 0 or count[n] >= max_new_tokens emits nothing (a = 0).
+ * In place, with e = the number of tokens emitted: they are appended to hist[n] at hist_len[n] (writes at or beyond ld_hist are dropped), hist_len[n] and count[n]
+ * grow by e, unfinished[n] becomes 0 if an eos was emitted, and pos_rows[n] grows by e unless `first` -- the fed tokens that stand are the last emitted token and
+ * the accepted drafts, a + 1 less what the cuts took.  `first` != 0 is the pick after the prefill: Q = 1, no drafts, nothing was fed, the position stays.
+ * map (nullable, int64 [N * Q]; needs base int64 [N]): step row n * Q + j holds the state of the row's emitted token count[n] - 1 + j (count before the step); map
+ * receives base[n] + count[n] + j where that token stands (j < e, not `first`), else dump_row.  rec int32 [4][N]: unfinished | count | a | d after the step, one
+ * buffer for one device-to-host copy.  argmax_ws: int32 [N * Q].  Checked before the launch: non-NULL pointers and their alignment, N >= 1,
+ * 1 <= Q <= LLMSEG_DECODE_CHUNK_MAX, 1 <= V < 2^31, ldl >= V, tok and draft_len as a pair (required for Q > 1), 1 <= ld_hist <= LLMSEG_LOGITS_HIST_CAP,
+ * max_new_tokens >= 1. */
+int llmseg_lookup_accept(const void* logits, int64_t ldl, int64_t N, int32_t Q, int64_t V, const int64_t* tok /* nullable */, const int32_t* draft_len /* nullable */,
+                         int32_t first, int64_t eos_token, int32_t max_new_tokens, int64_t* hist, int64_t ld_hist, int32_t* hist_len /* in/out */,
+                         int32_t* pos_rows /* in/out */, int32_t* unfinished /* in/out */, int32_t* count /* in/out */, const int64_t* base /* nullable */,
+                         int64_t dump_row, int64_t* map /* nullable */, int32_t* rec, int32_t* argmax_ws, void* stream);
 
 /* y[i] = act(x[i]), bf16, n % 8 == 0, in place allowed (the GELU between LayerNorm2d and the second transposed convolution of SAM's
  * mask decoder, mask_decoder.py:53-63: every other activation on the path rides in a GEMM epilogue) */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLMSEG_LIB") or os.path.join(_HERE, "libllmseg_hip.so")     # LLMSEG_LIB: side builds of the same ABI (tools/ experiments)
 
-ABI_VERSION = 21         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
+ABI_VERSION = 22         # == LLMSEG_ABI_VERSION of include/llmseg_hip.h
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SILU, ACT_SIGMOID = range(6)
 NOT_TAKEN = 1             # LLMSEG_NOT_TAKEN
@@ -122,6 +122,9 @@ SIGNATURES = {
     "llmseg_decode_attn_beams": [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _i32, _i32, _f32, _p, _i64, _p, _i64, _p],
     "llmseg_kv_quantize_mxfp8": [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p],
     "llmseg_decode_attn_mxfp8": [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _i32, _f32, _p, _i64, _p, _i64, _p],
+    "llmseg_decode_attn_chunk": [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i32, _i32, _i32, _f32, _p, _i64, _p, _i64, _p],
+    "llmseg_lookup_draft": [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _p, _i64, _p, _p, _p],
+    "llmseg_lookup_accept": [_p, _i64, _i64, _i32, _i64, _p, _p, _i32, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
     "llmseg_beam_step": [_p, _i64, _p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
     "llmseg_swiglu": [_p, _p, _i64, _i64, _i64, _i64, _p],
     "llmseg_act": [_p, _p, _i64, _i32, _p],

@@ -6,7 +6,7 @@ HERE="$(cd "$(dirname "$0")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
 OUT="${LLMSEG_OUT:-$ROOT/llmseg_amd/libllmseg_hip.so}"      # LLMSEG_OUT: side builds for experiments (tools/)
 OBJ="${LLMSEG_OBJ:-$ROOT/build/obj}"                          # build/ is git-ignored and gpurun-ignored
-SRCS="gemm.hip decode_gemm.hip sample.hip logits.hip beam.hip attention.hip decode_attn.hip kv_quant.hip attention_bwd.hip pointwise.hip head.hip sam_prompt.hip head_f32.hip backward.hip lora.hip targets.hip image.hip capi.cpp"
+SRCS="gemm.hip decode_gemm.hip sample.hip logits.hip lookup.hip beam.hip attention.hip decode_attn.hip kv_quant.hip attention_bwd.hip pointwise.hip head.hip sam_prompt.hip head_f32.hip backward.hip lora.hip targets.hip image.hip capi.cpp"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$ROOT/include -I$HERE $*"
 mkdir -p "$OBJ"
 SIG="$(echo "$FLAGS" | md5sum | cut -c1-8)"

@@ -262,7 +262,183 @@ int decode_attn_launch(bool table, const Mx8Scales* mx, const void* qkv, int64_t
   return LLMSEG_OK;
 }
 
+// ---- Q tokens per sequence in one step (generate(prompt_lookup_num_tokens=): the last emitted token and up to Q - 1 drafts) ----
+// Query j of sequence n sits at position pos + j and attends to keys 0 .. pos + j.  The lane mapping is the one above -- 16 lanes own a key, 8 dims each, a trip
+// of 64 keys with every K and V row requested together -- and a cached row, once in registers, serves all QN queries: QN * 8 query values, QN * 8 accumulators
+// and QN running (max, sum) pairs per lane (78 registers at QN = 1, 166 at 4, 256 at 7, 256 + 38 AGPRs at 8, no spills: one to six waves per SIMD, of which the
+// workgroup needs one).  The QN new keys and values never come from the
+// cache: EVERY workgroup of the head rotates them into LDS and takes keys pos .. pos + QN - 1 from there, so no workgroup reads a slot that another one writes
+// in this launch; the workgroup of split 0 alone stores them, with the bits QN successive llmseg_decode_attn_rows steps store (the same rope_lo / rope_hi, the
+// same f2bf; v is a copy).  Key split and merge are the existing scheme with the partials laid out per STEP ROW n * QN + j, which is what the merge kernel
+// above reads for N * QN rows.  A query with no key in a split leaves (max, sum) = (-1e30, 0): the merge weighs it with exp(-1e30 - M) = 0.
+// Rejected drafts: after the step the accept launch moves pos to pos + a + 1 <= pos + QN, so slots at or beyond the new position hold keys of tokens that are
+// not part of the sequence.  That is sound for the reason the prefill's comment gives: the next step writes QN slots from the new position on before any
+// query's key count reaches them (query j reads keys < pos' from the cache and keys pos' .. pos' + j from LDS), so a stale slot is overwritten before it is read.
+struct ChunkP {
+  const bf16_t* qkv; long ld;
+  const float *cs, *sn;
+  bf16_t *kc, *vc; long cstride;
+  const int32_t* pos_dev;
+  int heads, splits, capacity;
+  float scale;
+  bf16_t* out; long ldo;
+  float* part;                                         // [N * QN][heads][splits][130]
+};
+
+template <int QN>
+__global__ __launch_bounds__(256) void decode_attn_chunk_kernel(ChunkP p) {
+  constexpr int HD = 128, UN = 4;
+  __shared__ float qs[QN][HD];
+  __shared__ __align__(16) bf16_t knew[QN][HD], vnew[QN][HD];
+  __shared__ float red[4][QN][HD], rm[4][QN], rl[4][QN];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = tid >> 4, c = tid & 15;
+  const int h = blockIdx.x / p.splits, sp = blockIdx.x - h * p.splits, n = blockIdx.y;
+  const long D = (long)p.heads * HD;
+  const int pos = p.pos_dev[n], nk = pos + QN;            // workgroup-uniform: a scalar load.  Keys 0 .. pos + QN - 1, query j sees those <= pos + j
+  const int per = ((nk + p.splits - 1) / p.splits + 15) & ~15;
+  const int j0 = sp * per, j1 = min(nk, j0 + per);
+  bf16_t* kb = p.kc + (long)n * p.cstride + (long)h * HD;
+  bf16_t* vb = p.vc + (long)n * p.cstride + (long)h * HD;
+  // the QN new tokens: q and k rotated at pos + j, v copied, all into LDS; split 0 stores k and v (a slot at or beyond the capacity is not written)
+  for (int t = tid; t < QN * 192; t += 256) {
+    const int j = t / 192, r = t - j * 192, i = r & 63;
+    const bf16_t* row = p.qkv + ((long)n * QN + j) * p.ld + (long)h * HD;
+    const int pj = pos + j;
+    const bool store = sp == 0 && pj < p.capacity;
+    if (r < 128) {
+      const bf16_t* src = row + (r < 64 ? 0 : D);
+      const float a = bf2f(src[i]), b = bf2f(src[i + 64]);
+      const long ti = (long)min(pj, p.capacity - 1) * 64 + i;
+      const float cv = p.cs[ti], sv = p.sn[ti];
+      const bf16_t o1 = f2bf(rope_lo(a, b, cv, sv)), o2 = f2bf(rope_hi(a, b, cv, sv));
+      if (r < 64) { qs[j][i] = bf2f(o1); qs[j][i + 64] = bf2f(o2); }
+      else {
+        knew[j][i] = o1; knew[j][i + 64] = o2;
+        if (store) { kb[(long)pj * D + i] = o1; kb[(long)pj * D + i + 64] = o2; }
+      }
+    } else {
+      const bf16_t v1 = row[2 * D + i], v2 = row[2 * D + i + 64];
+      vnew[j][i] = v1; vnew[j][i + 64] = v2;
+      if (store) { vb[(long)pj * D + i] = v1; vb[(long)pj * D + i + 64] = v2; }
+    }
+  }
+  __syncthreads();
+  float q[QN][8], acc[QN][8], m[QN], l[QN];
+#pragma unroll
+  for (int jq = 0; jq < QN; ++jq) {
+    m[jq] = -1e30f; l[jq] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { q[jq][e] = qs[jq][c * 8 + e]; acc[jq][e] = 0.f; }
+  }
+  for (int jb = j0; jb < j1; jb += 16 * UN) {
+    uint4 kk[UN], vv[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int j = jb + u * 16 + g;
+      kk[u] = make_uint4(0, 0, 0, 0); vv[u] = kk[u];
+      if (j < j1) {
+        if (j >= pos) { kk[u] = *reinterpret_cast<const uint4*>(&knew[j - pos][c * 8]); vv[u] = *reinterpret_cast<const uint4*>(&vnew[j - pos][c * 8]); }
+        else { kk[u] = *reinterpret_cast<const uint4*>(kb + (long)j * D + c * 8); vv[u] = *reinterpret_cast<const uint4*>(vb + (long)j * D + c * 8); }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int j = jb + u * 16 + g;
+      float kf[8], vf[8];
+      unpack8(kk[u], kf);
+      unpack8(vv[u], vf);
+#pragma unroll
+      for (int jq = 0; jq < QN; ++jq) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s = fmaf(q[jq][e], kf[e], s);
+        s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
+        const bool valid = j < j1 && j <= pos + jq;
+        s = valid ? s * p.scale : -1e30f;
+        const float mn = fmaxf(m[jq], s), corr = __expf(m[jq] - mn), pj = valid ? __expf(s - mn) : 0.f;
+        l[jq] = l[jq] * corr + pj;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[jq][e] = acc[jq][e] * corr + pj * vf[e];
+        m[jq] = mn;
+      }
+    }
+  }
+  // per query: the four key groups of a wave, then the four waves
+#pragma unroll
+  for (int jq = 0; jq < QN; ++jq) {
+    float mw = fmaxf(m[jq], __shfl_xor(m[jq], 16));
+    mw = fmaxf(mw, __shfl_xor(mw, 32));
+    const float f = __expf(m[jq] - mw);
+    float lq = l[jq] * f;
+    lq += __shfl_xor(lq, 16); lq += __shfl_xor(lq, 32);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float a = acc[jq][e] * f;
+      a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
+      if (lane < 16) red[wave][jq][c * 8 + e] = a;
+    }
+    if (lane == 0) { rm[wave][jq] = mw; rl[wave][jq] = lq; }
+  }
+  __syncthreads();
+  for (int t = tid; t < QN * HD; t += 256) {
+    const int jq = t >> 7, d = t & 127;
+    const float M = fmaxf(fmaxf(rm[0][jq], rm[1][jq]), fmaxf(rm[2][jq], rm[3][jq]));
+    float L = 0.f, o = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const float e = __expf(rm[w][jq] - M); L += e * rl[w][jq]; o += e * red[w][jq][d]; }
+    const long srow = (long)n * QN + jq;
+    if (p.splits == 1) p.out[srow * p.ldo + (long)h * HD + d] = f2bf(o / L);
+    else {
+      float* pp = p.part + ((srow * p.heads + h) * p.splits + sp) * 130;
+      pp[d] = o;
+      if (d == 0) { pp[128] = M; pp[129] = L; }
+    }
+  }
+}
+
+template <int QN>
+void decode_attn_chunk_instance(const dim3& grid, hipStream_t stream, const ChunkP& p) {
+  LL_LAUNCH_KERNEL((decode_attn_chunk_kernel<QN>), grid, dim3(256), 0, stream, p);
+}
+
 }  // namespace
+
+// Q tokens per sequence: qkv [N * Q][ld], step row n * Q + j = token j of sequence n at position pos_rows_dev[n] + j
+extern "C" int llmseg_decode_attn_chunk(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
+                                        const int32_t* pos_rows_dev, int64_t capacity, int64_t N, int32_t Q, int32_t heads, int32_t head_dim, float scale,
+                                        void* out, int64_t ldo, void* scratch, int64_t scratch_bytes, void* stream) {
+  LL_CHECK(qkv && cos && sin && kcache && vcache && pos_rows_dev && out && N > 0 && N < 65536 && heads > 0, "decode_attn_chunk: bad arguments");
+  LL_CHECK(head_dim == 128, "decode_attn_chunk: head_dim 128 only");
+  LL_CHECK(Q >= 1 && Q <= LLMSEG_DECODE_CHUNK_MAX && N * Q < 65536, "decode_attn_chunk: Q must be in [1, %d] and N * Q < 65536, got Q = %d", LLMSEG_DECODE_CHUNK_MAX, (int)Q);
+  LL_CHECK((ld & 7) == 0 && (cache_stride_n & 7) == 0 && AL16(qkv) && AL16(kcache) && AL16(vcache), "decode_attn_chunk: 16-byte alignment required");
+  LL_CHECK(capacity >= Q && capacity <= 0x7fffffffL && cache_stride_n >= capacity * (int64_t)heads * 128,
+           "decode_attn_chunk: need Q <= capacity and cache_stride_n >= capacity * heads * 128 (capacity %ld, stride %ld)", (long)capacity, (long)cache_stride_n);
+  LL_CHECK(ld >= 3 * (int64_t)heads * 128 && ldo >= (int64_t)heads * 128, "decode_attn_chunk: ld %ld / ldo %ld too small for %d heads", (long)ld, (long)ldo, (int)heads);
+  int splits = 1;
+  if (scratch) {
+    splits = (int)std::min<int64_t>(16, std::max<int64_t>(1, 256 / (N * heads)));
+    while (splits > 1 && (int64_t)N * Q * heads * splits * 130 * 4 > scratch_bytes) --splits;
+  }
+  const ChunkP p{(const bf16_t*)qkv, (long)ld, cos, sin, (bf16_t*)kcache, (bf16_t*)vcache, (long)cache_stride_n, pos_rows_dev, heads, splits, (int)capacity, scale,
+                 (bf16_t*)out, (long)ldo, (float*)scratch};
+  const dim3 grid(heads * splits, (unsigned)N);
+  switch (Q) {
+    case 1: decode_attn_chunk_instance<1>(grid, (hipStream_t)stream, p); break;
+    case 2: decode_attn_chunk_instance<2>(grid, (hipStream_t)stream, p); break;
+    case 3: decode_attn_chunk_instance<3>(grid, (hipStream_t)stream, p); break;
+    case 4: decode_attn_chunk_instance<4>(grid, (hipStream_t)stream, p); break;
+    case 5: decode_attn_chunk_instance<5>(grid, (hipStream_t)stream, p); break;
+    case 6: decode_attn_chunk_instance<6>(grid, (hipStream_t)stream, p); break;
+    case 7: decode_attn_chunk_instance<7>(grid, (hipStream_t)stream, p); break;
+    default: decode_attn_chunk_instance<8>(grid, (hipStream_t)stream, p); break;
+  }
+  LL_LAUNCH_CHECK("decode_attn_chunk");
+  if (splits > 1) {
+    LL_LAUNCH_KERNEL(decode_attn_merge_kernel, dim3(heads, (unsigned)(N * Q)), dim3(128), 0, (hipStream_t)stream, (const float*)scratch, heads, splits, (bf16_t*)out, (long)ldo);
+    LL_LAUNCH_CHECK("decode_attn_chunk_merge");
+  }
+  return LLMSEG_OK;
+}
 
 extern "C" int llmseg_decode_attn(const void* qkv, int64_t ld, const float* cos, const float* sin, void* kcache, void* vcache, int64_t cache_stride_n,
                                   const int32_t* pos_dev, int64_t N, int32_t heads, int32_t head_dim, float scale, void* out, int64_t ldo,

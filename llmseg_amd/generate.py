@@ -160,6 +160,36 @@ def _check_sampling(do_sample, temperature, top_k, top_p, seed, uniforms, return
     return dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, uniforms=uniforms, return_logprobs=return_logprobs)
 
 
+def _check_lookup(model, prompt_lookup_num_tokens, max_matching_ngram_size, forced, trace, input_ids, max_new_tokens, do_sample, num_beams, controls, kv, fuse_decode):
+    """generate()'s prompt-lookup arguments, checked -> None when the mode is off (it takes none of the others), else (k, max_matching_ngram_size)."""
+    k, g = prompt_lookup_num_tokens, max_matching_ngram_size
+    if not (isinstance(g, int) and not isinstance(g, bool) and g >= 1):
+        raise ValueError(f"max_matching_ngram_size must be an integer >= 1, got {g!r}")
+    if k is None:
+        if g != 2 or forced is not None or trace is not None:
+            raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens (the mode is off without it)")
+        return None
+    if not (isinstance(k, int) and not isinstance(k, bool) and 1 <= k < ops.DECODE_CHUNK_MAX):
+        raise ValueError(f"prompt_lookup_num_tokens must be None (off) or an integer in [1, {ops.DECODE_CHUNK_MAX - 1}] (k + 1 <= {ops.DECODE_CHUNK_MAX} rows a step keep one "
+                         f"sequence on the skinny GEMM), got {k!r}")
+    if do_sample:
+        raise ValueError("prompt_lookup_num_tokens with do_sample is out of scope: verifying drafts against a sampled token is speculative sampling, another accept rule")
+    if isinstance(num_beams, int) and num_beams >= 2:
+        raise ValueError("prompt_lookup_num_tokens with num_beams >= 2 is out of scope: a draft belongs to one hypothesis, the beams re-order every step")
+    if controls is not None:
+        raise ValueError("prompt_lookup_num_tokens with repetition_penalty, no_repeat_ngram_size, min_new_tokens or suppress_tokens is out of scope: the processors "
+                         "would have to rewrite the logits of every drafted position under its own history")
+    if kv:
+        raise ValueError("prompt_lookup_num_tokens with kv_format is out of scope: the MXFP8 cache would need a further instance of the chunk attention kernel")
+    if not fuse_decode:
+        raise ValueError("prompt_lookup_num_tokens needs fuse_decode=True (the chunk attention step is built into the fused decode step only)")
+    if model.config.llama.head_dim != 128:
+        raise ValueError(f"prompt_lookup_num_tokens needs head_dim 128, got {model.config.llama.head_dim}: the two-launch route is out of scope")
+    if forced is not None and (not torch.is_tensor(forced) or forced.dtype != torch.int64 or tuple(forced.shape) != (input_ids.shape[0], max_new_tokens)):
+        raise ValueError(f"_lookup_forced must be an int64 tensor [N, max_new_tokens] = {(input_ids.shape[0], max_new_tokens)}")
+    return k, g
+
+
 def _row_prompts(model, input_ids, attention_mask, fuse_decode, fill, controls, max_new_tokens):
     """The row loop's prompts, checked where the trimmed mask is known -> (input_ids, attention_mask, lens): trimmed to the longest prompt, the padding set to `fill`,
     lens = the prompt lengths L_i on the host; (input_ids, None, None) on the uniform route."""
@@ -303,9 +333,11 @@ class DecodeState:
     """Everything a decode step touches, at fixed addresses (so the step can be captured once and replayed): the KV cache
     [layers][N, capacity, H] bf16 x 2, the device-side position {pos, pos + 1} (or one position per sequence, pos_rows, when the prompts
     differ in length), the step's input embeddings and its outputs.  kv = ("kv", "mxfp8", "packed"): K and V are uint8 E4M3 codes, with their E8M0 scale bytes
-    ks, vs [layers][N, capacity, H / 32]; ("kv", "mxfp8", "bf16"): the bf16 cache, which then holds x_hat (the yardstick of the packed cache)."""
+    ks, vs [layers][N, capacity, H / 32]; ("kv", "mxfp8", "bf16"): the bf16 cache, which then holds x_hat (the yardstick of the packed cache).
+    q > 1 (prompt lookup): a step feeds q tokens per sequence, so x, hidden and logits hold N * q step rows (row n * q + j = token j of sequence n) while the cache
+    stays [N, capacity]; the step reads pos_rows and does not advance it (the accept launch does)."""
 
-    def __init__(self, layers, N, cap, H, V, device, kv=()):
+    def __init__(self, layers, N, cap, H, V, device, kv=(), q=1):
         self.kv_format, self.kv_packed = (kv[1], kv[2] == "packed") if kv else (None, False)
         self.k = torch.empty((layers, N, cap, H), device=device, dtype=torch.uint8 if self.kv_packed else BF16)
         self.v = torch.empty_like(self.k)
@@ -315,9 +347,10 @@ class DecodeState:
             self.vs = torch.empty_like(self.ks)
         self.pos = torch.zeros((2,), device=device, dtype=torch.int32)       # [0] = position of the token being fed, [1] = keys present after it
         self.pos_rows = torch.zeros((N,), device=device, dtype=torch.int32)  # ragged prompts: position of the token being fed, per sequence
-        self.x = torch.empty((N, H), device=device, dtype=BF16)
-        self.hidden = torch.empty((N, H), device=device, dtype=BF16)
-        self.logits = torch.empty((N, V), device=device, dtype=BF16)
+        self.q, self.rows = q, N * q                                          # tokens per sequence and step; rows of a step
+        self.x = torch.empty((self.rows, H), device=device, dtype=BF16)
+        self.hidden = torch.empty((self.rows, H), device=device, dtype=BF16)
+        self.logits = torch.empty((self.rows, V), device=device, dtype=BF16)
         self.N, self.cap, self.H = N, cap, H
         self.graph = None
         self.warm = False            # the state's first step ran eagerly (the step is captured at its second)
@@ -373,7 +406,9 @@ class GenerateMixin:
         cos, sin, _ = self._rope(st.cap)
         x = st.x
         att = torch.empty((N, H), device=x.device, dtype=BF16)
-        scratch = ops.decode_attn_scratch(N, c.heads, x.device) if st.fused and c.head_dim == 128 else None
+        scratch = ops.decode_attn_scratch(st.N, c.heads, x.device) if st.fused and c.head_dim == 128 else None
+        if scratch is not None and st.q > 1:                   # the same key split, partials per step row
+            scratch = torch.empty((scratch.numel() * st.q,), device=x.device, dtype=torch.float32)
         for i in range(c.layers):
             qkv = lin(i, "qkv", x, norm="input_layernorm.weight")
             self._decode_attention(st, i, qkv, cos, sin, att, scratch)
@@ -382,12 +417,16 @@ class GenerateMixin:
             x = lin(i, "mlp.down_proj.weight", gu, swiglu=True, residual=x)
         ops.norm(x, self._w("model.norm.weight", F), None, eps=c.eps, rms=True, out=st.hidden)
         ops.gemm(st.hidden, self._w("lm_head.weight", F), out=st.logits)          # lm_head stays bf16 at weight_bits = 8 too: 2 % of the stream, and it decides the arg-max
-        (st.pos_rows if st.ragged else st.pos).add_(1)
+        if st.q == 1:                                          # (q > 1: the accept launch advances pos_rows by what stands of the chunk)
+            (st.pos_rows if st.ragged else st.pos).add_(1)
 
     def _decode_attention(self, st, i, qkv, cos, sin, att, scratch):
         """RoPE of the new token's q and k at the device-side position, its K / V appended to layer i's cache, attention of the one query over the cache -> att."""
         c = self.config.llama
         hd, heads, H = c.head_dim, c.heads, st.H
+        if st.q > 1:                                           # prompt lookup: q tokens per sequence at pos_rows[n] .. pos_rows[n] + q - 1, causal among themselves
+            ops.decode_attn_chunk(qkv, cos, sin, st.k[i], st.v[i], st.pos_rows, heads, hd, st.q, out=att, scratch=scratch)
+            return
         if st.fused and hd == 128:                             # one launch (+ the split's merge); ragged: every sequence at its own position (RoPE angle, cache slot, key count)
             pos = st.pos_rows if st.ragged else st.pos
             if st.kv_packed:                                   # the same step on the MXFP8 cache: slot [n][pos] receives the rounding of the new k / v
@@ -433,7 +472,7 @@ class GenerateMixin:
                 return st.qkv_w[i]
             return self._wcat(p + name, [p + m for m in members[name]], F) if name in members else self._w(p + name, F)
 
-        onload = st.fused and st.N == 1      # RMSNorm / SwiGLU on the skinny GEMM's A load: every wave redoes the transform, a win for one row only (two rows: 4.02 vs
+        onload = st.fused and st.rows == 1   # RMSNorm / SwiGLU on the skinny GEMM's A load: every wave redoes the transform, a win for one row only (two rows: 4.02 vs
         #                                      3.90 ms per token with the norm on load, 5.97 vs 4.34 with both): more rows keep the separate launches
         if onload:
             def lin_onload(i, name, a, norm=None, swiglu=False, residual=None):
@@ -554,11 +593,12 @@ class GenerateMixin:
             st.graph = g                                        # capture records, it does not execute: fall through to the replay
         st.graph.replay()
 
-    def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, mode, fused, key, kv=()):
+    def _prefill(self, images_clip, input_ids, attention_mask, rows, max_new_tokens, mode, fused, key, kv=(), chunk=1):
         """What every generate() route does before its loop: the prompts (input_ids [N, L], trimmed; attention_mask = the ragged call's mask, else None) through the prefill
         in the call's weight mode (`_weight_mode`), K and V of prompt n into physical row n * rows of the decode state of N * rows rows (rows = 1, or the beams per prompt), the state made ready
         for the call's route.  The states are kept per (N * rows, capacity) + key + kv (kv = `_check_kv`'s: a quantised cache is a state of its own, and K / V go into it
-        through `ops.kv_quantize_mxfp8`).  -> (state, final-norm hidden [N, T, H], T, embedding weights, lm_head weights)."""
+        through `ops.kv_quantize_mxfp8`).  chunk = q > 1 (prompt lookup): the state's steps take q tokens per sequence, and the capacity has room for a chunk behind
+        the last position.  -> (state, final-norm hidden [N, T, H], T, embedding weights, lm_head weights)."""
         self.prepare()
         c = self.config
         cl = c.llama
@@ -572,12 +612,12 @@ class GenerateMixin:
         proj = self.encode_images(images_clip.to(dev, BF16))
         emb_w = self._w("model.embed_tokens.weight", F)
         embeds = F.embed_splice(input_ids.to(dev).contiguous(), emb_w, proj[1:], Pn, (Pn + 1) * H, plan.tok_index)
-        cap = (T + max_new_tokens + 63) // 64 * 64
+        cap = (T + max_new_tokens + (chunk if chunk > 1 else 0) + 63) // 64 * 64      # chunk: pos_n + q <= cap at every step (pos_n <= T + max_new_tokens - 1)
         states = self.__dict__.setdefault("_decode_states", {})
         key = key + kv
         st = states.get((N * rows, cap) + key)
         if st is None:
-            st = states[(N * rows, cap) + key] = DecodeState(cl.layers, N * rows, cap, H, cl.vocab, dev, kv=kv)
+            st = states[(N * rows, cap) + key] = DecodeState(cl.layers, N * rows, cap, H, cl.vocab, dev, kv=kv, q=chunk)
 
         # ragged prompts: K and V are copied for [:, :T] of every row.  The slots at or beyond a row's own T_i = L_i - 1 + Pn then hold the padding's
         # K / V (and, past T, whatever an earlier call left): garbage that is never read, because the step that feeds a row's token at position
@@ -599,7 +639,7 @@ class GenerateMixin:
         else:
             st.qw = self._quantize_decode_weights(mode)
             hidden_p = self._prefill_quantised(embeds, plan.key_mask, st.qw, keep_kv)
-        ragged = attention_mask is not None or rows > 1       # beams: every row at its own device-side position (they are equal; the per-row kernels read them)
+        ragged = attention_mask is not None or rows > 1 or chunk > 1       # (chunk: likewise) beams: every row at its own device-side position (they are equal; the per-row kernels read them)
         if fused != st.fused or mode != st.bits or ragged != st.ragged:
             st.fused, st.bits, st.ragged, st.graph, st.warm = fused, mode, ragged, None, False      # a different kernel sequence: capture again
         st.qkv_w = self._merge_lora() if (fused and cl.lora_r > 0 and mode is None) else None
@@ -609,7 +649,8 @@ class GenerateMixin:
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, pad_token_id=0, use_graph=True, fuse_decode=True,
                  weight_bits=None, attention_mask=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None,
                  return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False, return_beam_scores=False, beam_cache="indirect", _beam_trace=None,
-                 weight_format=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, kv_format=None, kv_cache="packed"):
+                 weight_format=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, kv_format=None, kv_cache="packed", prompt_lookup_num_tokens=None,
+                 max_matching_ngram_size=2, _lookup_forced=None, _lookup_trace=None):
         """Greedy generation (or sampling: do_sample, or beam search: num_beams, both below).  images_clip bf16 [N, 3, 224, 224] (one image per sequence), input_ids int64 [N, L] holding exactly one
         IMAGE_TOKEN_INDEX each.
         -> (sequences int64 [N, L + n_new], hidden bf16 [N, T + n_new - 1, H]: final-norm hidden state of every token but the last).
@@ -684,13 +725,39 @@ class GenerateMixin:
         kernel keeps the bf16 instance's lane mapping and spends on the unpack what it saves on the load; what the format buys today is the memory (half the cache).
         After 512 more tokens (833 .. 865 keys) the picture is the same: 3.40 / 5.66 against 3.40 / 5.53 at 1 / 8 sequences, 8.43 against 7.28 at 3 x 16 beams.
         The quantiser adds nothing measurable to the prefill.  Accuracy: E4M3 keeps four significant bits of every cached value; on the tiny test model the
-        hidden states differ from the oracle by up to 0.38 (bf16 cache: 0.15) at |h| <= 6.1."""
+        hidden states differ from the oracle by up to 0.38 (bf16 cache: 0.15) at |h| <= 6.1.
+        prompt_lookup_num_tokens = k (an integer 1 .. 7; None = off, the default) with max_matching_ngram_size = g (>= 1, default 2): prompt-lookup decoding, Hugging Face's
+        `generate(prompt_lookup_num_tokens=)`.  Per step and row the draft launch (`ops.lookup_draft`) finds the tail n-gram of the row's own history -- its prompt ids as
+        given, then what it emitted -- earlier in that history (the longest n-gram <= g that occurs, its earliest occurrence) and drafts the up to k ids behind it; the last
+        emitted token and the drafts are Q = k + 1 query rows of ONE decode step (`ops.decode_attn_chunk`: a cached K / V row is loaded once for all Q queries), and the
+        accept launch (`ops.lookup_accept`) keeps the longest prefix of drafts that the step's own arg-maxes confirm plus one more token.  Semantics: every emitted token is
+        the arg-max of the logits THIS call computed at the position before it, the lowest index among equal values as `torch.argmax`; the call is therefore a greedy
+        continuation under the verify step's arithmetic.  It is not bit-identical to the plain route, whose GEMMs see another row count; it agrees with the plain route and
+        with the oracle wherever the choice is decidable (the margin rule of tests/generate_checks.py).  Rows advance at different speeds, so both results have the
+        per-row, left-aligned layouts of the attention_mask route also when the prompts are equal in length: sequences [N, Lm + n_new] with n_new the largest number of
+        tokens any row emitted -- row i holds its prompt, its count_i tokens (eos included), then pad_token_id: the tokens and the shape the plain route returns -- and
+        hidden [N, Tm + n_new - 1, H]: row i's T_i prefill states, the state of each token it emitted but its last, then zeros.  The plain route goes on feeding
+        pad_token_id to a finished row and returns those states; this mode does not (`seg_embeddings` reads rows in front of a [SEG] only and is unaffected).  It composes
+        with attention_mask, weight_bits=8, weight_format="mxfp4", use_graph, eos_token_id / pad_token_id and max_new_tokens.  The history is that of the logits controls:
+        Lm + max_new_tokens must not exceed `ops.LOGITS_HIST_CAP`.  N * Q <= 8 step rows stay on the skinny GEMM and on one quantised-GEMM call -- the intended shape is
+        one sequence; more rows go where `ops.gemm` and `ops.gemm_rows` send them (the tile GEMM, or 8-row chunks that stream the weights again): correct and slower.
+        Out of scope (ValueError): do_sample, num_beams >= 2, the four logits controls, kv_format, fuse_decode=False, head_dim != 128.  With the argument at None not
+        one launch of the routes above changes.  `_lookup_forced` (int64 [N, max_new_tokens]: the drafts of a row that has emitted c tokens are forced[n, c : c + k]) and
+        `_lookup_trace` (a list that receives per step the rows' draft lengths and accepted counts) are test hooks.  Measured at Llama-7B, one sequence, 64-token prompt, alternating with the plain route in one
+        session (profiles/prompt_lookup.md): a step costs 3.98 / 4.41 / 5.27 ms at k = 1 / 3 / 7 against the plain step's 3.35 (MXFP4 rows: 2.80 / 3.12 / 3.62 against 2.06), so
+        with every draft accepted a token costs 2.01 / 1.11 / 0.67 ms (0.45 with MXFP4 rows at k = 7) and with none 19 / 31 / 57 % more than on the plain route; break-even is
+        0.19 / 0.31 / 0.57 accepted drafts per step (MXFP4: 0.36 / 0.51 / 0.76).  At 8 sequences and k = 3 (32 rows, the tile GEMM) a step costs 5.67 ms against 5.03, and a
+        batch ends with its slowest row.  The quantised routes at N * Q > 8 were not measured."""
         controls = _check_controls(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens, num_beams)
         _check_beams(self, num_beams, length_penalty, early_stopping, return_beam_scores, beam_cache, _beam_trace, do_sample, fuse_decode)
         sampling = _check_sampling(do_sample, temperature, top_k, top_p, seed, uniforms, return_logprobs, input_ids, max_new_tokens)
         mode = _weight_mode(weight_bits, weight_format, fuse_decode)
         kv = _check_kv(self, kv_format, kv_cache, fuse_decode)
+        lookup = _check_lookup(self, prompt_lookup_num_tokens, max_matching_ngram_size, _lookup_forced, _lookup_trace, input_ids, max_new_tokens, do_sample, num_beams,
+                               controls, kv, fuse_decode)
         fill = 0 if pad_token_id is None else int(pad_token_id)      # what finished rows and the padding hold
+        if lookup is not None:
+            return self._generate_lookup(images_clip, input_ids, attention_mask, max_new_tokens, eos_token_id, fill, use_graph, mode, lookup, _lookup_forced, _lookup_trace)
         if num_beams >= 2:
             return self._generate_beams(images_clip, input_ids, max_new_tokens, eos_token_id, fill, use_graph, mode, attention_mask, num_beams, float(length_penalty),
                                         early_stopping, return_beam_scores, beam_cache, _beam_trace, kv)
@@ -719,6 +786,68 @@ class GenerateMixin:
             logits = st.logits
         res = pack(seqs, n_new)
         return res + (torch.cat([lp[:, None] for lp in live.logprobs], 1),) if sampling is not None and sampling["return_logprobs"] else res
+
+    def _generate_lookup(self, images_clip, input_ids, attention_mask, max_new_tokens, eos_token_id, fill, use_graph, mode, lookup, forced, trace):
+        """`generate(prompt_lookup_num_tokens=k)`: the arguments are checked there.  Per step: the draft launch, the embedding gather of N * Q tokens, the decode step on
+        N * Q rows (captured), the accept launch, one index_copy_ of the step's states into the packed result, one small device-to-host copy.  The first pick after the
+        prefill is the accept launch with Q = 1 and no drafts: one pick rule, one eos rule."""
+        k, g = lookup
+        Q = k + 1
+        lens = None
+        if attention_mask is not None:
+            input_ids, attention_mask, lens = self._ragged_prompts(input_ids, attention_mask)
+        if lens is not None:
+            input_ids = torch.where(attention_mask.to(input_ids.device), input_ids, torch.full_like(input_ids, fill))
+        N, L = input_ids.shape
+        if L + max_new_tokens > ops.LOGITS_HIST_CAP:
+            raise ValueError(f"prompt_lookup_num_tokens drafts from a history of prompt + max_new_tokens = {L} + {max_new_tokens} ids per row: more than the cap of "
+                             f"{ops.LOGITS_HIST_CAP}")
+        # a state of its own: no other route meets its step rows or its graph
+        st, hidden_p, T, emb_w, lm_w = self._prefill(images_clip, input_ids, attention_mask, 1, max_new_tokens, mode, True, ("lookup", Q), (), chunk=Q)
+        dev = self.device_
+        H, V, Pn = self.config.llama.hidden, self.config.llama.vocab, self.config.n_img_tokens
+        if lens is None:
+            lens = torch.full((N,), L, dtype=torch.int64)
+        t_rows = (lens - 1 + Pn).to(dev)                       # T_i: row i's prefill length = the position of its first fed token
+        st.pos_rows.copy_(t_rows.to(torch.int32))
+        rows = T + max_new_tokens - 1
+        flat = torch.zeros((N * rows + 1, H), device=dev, dtype=BF16)      # the packed result, row by row, and one dump row for the states of tokens that do not stand
+        hidden = flat[:N * rows].view(N, rows, H)
+        own = torch.arange(T, device=dev)[None, :] < t_rows[:, None]
+        hidden[:, :T] = torch.where(own[:, :, None], hidden_p, torch.zeros_like(hidden_p))
+        logits = ops.gemm(ops.gather_rows(hidden_p.reshape(N * T, H), torch.arange(N, device=dev) * T + t_rows - 1), lm_w)      # each row's own last prompt position
+        base = torch.arange(N, device=dev) * rows + t_rows - 1           # + count + j: the flat row of `hidden` for the state of step row j
+        hist = torch.zeros((N, L + max_new_tokens), dtype=torch.int64, device=dev)      # each row's history, left-aligned: its prompt, then what it emitted
+        hist[:, :L] = input_ids.to(dev)
+        hist_len = lens.to(torch.int32).to(dev)
+        count = torch.zeros((N,), dtype=torch.int32, device=dev)
+        unfinished = torch.ones((N,), dtype=torch.int32, device=dev)
+        tok = torch.empty((N, Q), dtype=torch.int64, device=dev)
+        draft_len = torch.empty((N,), dtype=torch.int32, device=dev)
+        hmap = torch.empty((N * Q,), dtype=torch.int64, device=dev)
+        rec = torch.empty((4, N), dtype=torch.int32, device=dev)
+        ws = torch.empty((N * Q,), dtype=torch.int32, device=dev)
+        forced = None if forced is None else forced.to(dev).contiguous()
+        state = dict(hist=hist, hist_len=hist_len, pos_rows=st.pos_rows, unfinished=unfinished, count=count, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                     rec=rec, workspace=ws)
+        ops.lookup_accept(logits, None, None, first=True, **state)
+        while True:
+            rec_h = rec.cpu()                                  # the one host synchronisation of a step
+            if not bool(((rec_h[0] != 0) & (rec_h[1] < max_new_tokens)).any()):      # every row finished or full
+                break
+            ops.lookup_draft(hist, hist_len, count, unfinished, k, g, max_new_tokens, V, fill, forced=forced, tok=tok, draft_len=draft_len)
+            st.x.copy_(ops.gather_rows(emb_w, tok.view(-1)))
+            self._decode_step(st, use_graph)
+            ops.lookup_accept(st.logits, tok, draft_len, base=base, dump_row=N * rows, map=hmap, **state)
+            flat.index_copy_(0, hmap, st.hidden)
+            if trace is not None:
+                r = rec.cpu()
+                trace.append(dict(draft_len=r[3].tolist(), accepted=r[2].tolist()))
+        counts = rec_h[1].to(torch.int64)
+        n_new = int(counts.max())
+        keep = torch.arange(L + n_new)[None, :] < (lens + counts)[:, None]
+        out = torch.where(keep.to(dev), hist[:, :L + n_new], torch.full_like(hist[:, :L + n_new], fill))      # row i: prompt, its count_i tokens, fill
+        return out, hidden[:, :T + n_new - 1]
 
     def _generate_beams(self, images_clip, input_ids, max_new_tokens, eos_token_id, fill, use_graph, mode, attention_mask, B, length_penalty, early_stopping,
                         return_beam_scores, beam_cache, trace, kv=()):

@@ -492,6 +492,90 @@ def decode_attn(qkv, cos, sin, kcache, vcache, pos_dev, heads, head_dim, out=Non
     return out
 
 
+DECODE_CHUNK_MAX = 8                # == LLMSEG_DECODE_CHUNK_MAX of include/llmseg_hip.h
+
+
+def decode_attn_chunk(qkv, cos, sin, kcache, vcache, pos_rows, heads, head_dim, Q, out=None, scale=None, scratch=None):
+    """`decode_attn(per_row=True)` for Q tokens per sequence in one launch (+ merge; `llmseg_decode_attn_chunk`): qkv [N * Q, 3 * heads * head_dim], step row n * Q + j
+    is token j of sequence n at position pos_rows[n] + j.  Its k (rotated) and v go to cache slot [n][pos_rows[n] + j] -- the bits Q successive decode_attn steps
+    write -- and out[n * Q + j] = attention of the rotated q over the keys 0 .. pos_rows[n] + j.  The caller keeps pos_rows[n] + Q <= capacity.  head_dim 128,
+    bf16 caches, 1 <= Q <= DECODE_CHUNK_MAX.  scratch: fp32 buffer of Q times `decode_attn_scratch(N, heads)` (None = one workgroup per head)."""
+    N = kcache.shape[0]
+    assert qkv.shape[0] == N * Q and 1 <= Q <= DECODE_CHUNK_MAX, (qkv.shape, N, Q)
+    assert kcache.shape == vcache.shape and kcache.dtype == vcache.dtype == BF16 and kcache.stride(1) == heads * head_dim and vcache.stride() == kcache.stride()
+    assert pos_rows.dtype == torch.int32 and pos_rows.numel() == N and pos_rows.is_contiguous()
+    cap = kcache.shape[1]
+    assert cos.shape[0] >= cap and sin.shape[0] >= cap and cos.dtype == sin.dtype == torch.float32
+    if out is None:
+        out = torch.empty((N * Q, heads * head_dim), device=qkv.device, dtype=BF16)
+    _lib.check(_lib.load().llmseg_decode_attn_chunk(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), max(kcache.stride(0), cap * kcache.stride(1)) if N == 1 else kcache.stride(0),
+                                                    _ptr(pos_rows), cap, N, int(Q), heads, head_dim, float(scale if scale is not None else head_dim ** -0.5), _ptr(out),
+                                                    out.stride(0), _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,
+                                                    _stream()), "decode_attn_chunk")
+    return out
+
+
+def _i32_rows(t, N):
+    return t.is_cuda and t.dtype == torch.int32 and t.shape == (N,) and t.is_contiguous()
+
+
+def lookup_draft(hist, hist_len, count, unfinished, k, max_matching_ngram_size, max_new_tokens, vocab, pad_token_id=0, forced=None, tok=None, draft_len=None):
+    """The draft launch of prompt-lookup decoding (`llmseg_lookup_draft`; the rule is stated in include/llmseg_hip.h): per row, the up to k ids that followed the
+    earliest earlier occurrence of the history's tail n-gram (the longest n-gram <= max_matching_ngram_size that has one), cut at max_new_tokens - count - 1 ids and
+    before an id outside [0, vocab).  hist int64 [N, cap <= LOGITS_HIST_CAP] (dense rows), hist_len / count / unfinished int32 [N].  forced (int64 [N, W]; a test hook):
+    the draft is forced[n, count[n]:] instead.  -> (tok int64 [N, k + 1] = the last id of the history, the draft, then pad_token_id; draft_len int32 [N])."""
+    N = hist.shape[0]
+    dev = hist.device
+    assert hist.is_cuda and hist.dtype == torch.int64 and hist.dim() == 2 and hist.stride(1) == 1 and (N == 1 or hist.stride(0) == hist.shape[1])
+    assert _i32_rows(hist_len, N) and _i32_rows(count, N) and _i32_rows(unfinished, N)
+    if forced is not None:
+        assert forced.is_cuda and forced.dtype == torch.int64 and forced.dim() == 2 and forced.shape[0] == N and forced.is_contiguous()
+    if tok is None:
+        tok = torch.empty((N, k + 1), device=dev, dtype=torch.int64)
+    if draft_len is None:
+        draft_len = torch.empty((N,), device=dev, dtype=torch.int32)
+    assert tok.is_cuda and tok.dtype == torch.int64 and tok.shape == (N, k + 1) and tok.is_contiguous() and _i32_rows(draft_len, N)
+    _lib.check(_lib.load().llmseg_lookup_draft(_ptr(hist), hist.shape[1], _ptr(hist_len), _ptr(count), _ptr(unfinished), N, int(k), int(max_matching_ngram_size),
+                                               int(max_new_tokens), int(vocab), 0 if pad_token_id is None else int(pad_token_id), _ptr(forced),
+                                               0 if forced is None else forced.shape[1], _ptr(tok), _ptr(draft_len), _stream()), "lookup_draft")
+    return tok, draft_len
+
+
+def lookup_accept(logits, tok, draft_len, hist, hist_len, pos_rows, unfinished, count, max_new_tokens, eos_token_id=None, first=False, base=None, dump_row=0, map=None,
+                  rec=None, workspace=None):
+    """The accept launch of prompt-lookup decoding (`llmseg_lookup_accept`, two launches; the rule is stated in include/llmseg_hip.h) on logits bf16 [N * Q, V] (rows
+    may be strided): a_n = the leading drafts tok[n, 1 + j] that equal argmax(logits[n * Q + j]); the row emits the arg-maxes of step rows 0 .. a_n, cut at
+    max_new_tokens and after the first eos.  IN PLACE: the emitted tokens join hist / hist_len, count grows, unfinished falls on eos, pos_rows advances by the number
+    emitted (not with first=True: the pick after the prefill, Q = 1, tok = draft_len = None).  map (int64 [N * Q], with base int64 [N] and dump_row): the row of the
+    packed hidden result that each step row's state belongs to (base[n] + count_before[n] + j), or dump_row.  -> rec int32 [4, N]: unfinished | count | accepted | draft
+    length after the step."""
+    _req(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    N = hist.shape[0]
+    Q = R // N
+    dev = logits.device
+    assert R == N * Q and 1 <= Q <= DECODE_CHUNK_MAX and (tok is None) == (draft_len is None) and (Q == 1 or tok is not None)
+    assert hist.is_cuda and hist.dtype == torch.int64 and hist.dim() == 2 and hist.stride(1) == 1 and (N == 1 or hist.stride(0) == hist.shape[1])
+    assert _i32_rows(hist_len, N) and _i32_rows(pos_rows, N) and _i32_rows(unfinished, N) and _i32_rows(count, N)
+    if tok is not None:
+        assert tok.is_cuda and tok.dtype == torch.int64 and tok.shape == (N, Q) and tok.is_contiguous() and _i32_rows(draft_len, N)
+    if map is not None:
+        assert map.is_cuda and map.dtype == torch.int64 and map.shape == (R,) and map.is_contiguous()
+        assert base is not None and base.is_cuda and base.dtype == torch.int64 and base.shape == (N,) and base.is_contiguous()
+    if rec is None:
+        rec = torch.empty((4, N), device=dev, dtype=torch.int32)
+    if workspace is None:
+        workspace = torch.empty((R,), device=dev, dtype=torch.int32)
+    assert rec.is_cuda and rec.dtype == torch.int32 and rec.shape == (4, N) and rec.is_contiguous()
+    assert workspace.is_cuda and workspace.dtype == torch.int32 and workspace.numel() >= R and workspace.is_contiguous()
+    _lib.check(_lib.load().llmseg_lookup_accept(_ptr(logits), max(logits.stride(0), V) if R == 1 else logits.stride(0), N, Q, V, _ptr(tok), _ptr(draft_len), 1 if first else 0,
+                                                -1 if eos_token_id is None else int(eos_token_id), int(max_new_tokens), _ptr(hist), hist.shape[1], _ptr(hist_len),
+                                                _ptr(pos_rows), _ptr(unfinished), _ptr(count), _ptr(base), int(dump_row), _ptr(map), _ptr(rec), _ptr(workspace),
+                                                _stream()), "lookup_accept")
+    return rec
+
+
 def beam_step(logits, beam_scores, done, src_in, src_out, pos_rows, num_beams, eos_token_id=None, pad_token_id=0, out=None, workspace=None):
     """One beam-search pick (`llmseg_beam_step`, two launches; the rule and its arithmetic are stated in include/llmseg_hip.h).  logits bf16
     [N * beams_in, V] (beams_in = 1: the first pick, else num_beams), beam_scores fp32 [N * beams_in], done int32 [N], src_in / src_out int32
